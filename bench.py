@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: equality scan of a 1e9-value 9-bit packed column per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (one scan_eq launch: bitmap + hit count) over the rank's
 row-range shard, the column already resident in HBM; no data-path collective inside the timed region.
 `value` is the headline of SURVEY 8e: ONE column of --rows rows (default 1e9) split over the N ranks at
-8192-row boundaries ("scaling": "strong").  The weak figure -- every rank its own --rows rows -- is
-measured in the same run and printed beside it (`weak_values_per_s`); at N = 1 they are one measurement.
-The RCCL bitmap gather is timed separately after the scans and reported as `gather_ms`; an exchange that
-fails or never returns still lets the scan line through, and then the run exits NON-ZERO (4 / 3).
+8192-row boundaries ("scaling": "strong").
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and
+prints the line.  --full adds everything else the benchmark measures:
+  * the CPU baseline on the same column (N = 1, scan_eq; whole-bitmap comparison with the GPU's);
+  * N > 1: the other partition -- weak: every rank its own --rows rows -- measured in the same run and
+    printed beside the headline (`weak_values_per_s`; at N = 1 the two are one measurement), and the
+    RCCL bitmap gather, timed after the scans and reported as `gather_ms`; an exchange that fails or
+    never returns still lets the scan line through, and then the run exits NON-ZERO (4 / 3).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "measurement" for every field).
 """
@@ -55,7 +60,49 @@ def parse():
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the multi-core CPU leg (0 = every CPU this process may use: affinity mask / cgroup quota)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline (N = 1), the other partition and the "
+                         "exchange step (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64; "
+                         "outputs above %d values as a fixed seeded sample, positions in DIR/<name>_index.npy)" % DUMP_MAX_VALUES)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_VALUES = 1 << 21  # per output: <= 2 Mi values + their float64 positions (<= 32 MB), two outputs at most
+DUMP_EDGE = 1 << 18        # the first and the last 256 Ki values are always in the sample (ragged ends)
+
+
+def dump_outputs(out_dir, outputs, prefix=""):
+    """Write each (name, tensor) of `outputs` to out_dir/<prefix><name>.npy.  A tensor is the logical output (a 2-D
+    tensor = rows of equal length, possibly a view with padding cut off).  Integer outputs of at most 8 bits go out as
+    float32, wider ones as float64 (exact up to 2^53).  Above DUMP_MAX_VALUES values, a fixed sample: both edges plus
+    draws of a seeded generator over the flattened positions, which depend only on the output's size, so the same
+    arguments give the same positions in every run; the positions go to <prefix><name>_index.npy."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs:
+        t2 = t.reshape(1, -1) if t.dim() <= 1 else t
+        rows, cols = t2.shape
+        total = rows * cols
+        fdt = np.float32 if t.element_size() == 1 else np.float64
+        if total <= DUMP_MAX_VALUES:
+            vals = t2.cpu().numpy().reshape(t.shape).astype(fdt)
+            idx = None
+        else:
+            rng = np.random.default_rng(20240917)
+            draws = rng.integers(DUMP_EDGE, total - DUMP_EDGE, DUMP_MAX_VALUES - 2 * DUMP_EDGE, dtype=np.int64)
+            idx = np.unique(np.concatenate([np.arange(DUMP_EDGE), draws, np.arange(total - DUMP_EDGE, total)]))
+            di = torch.from_numpy(idx).to(t2.device)
+            vals = t2[di // cols, di % cols].cpu().numpy().astype(fdt)
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), vals)
+        if idx is not None:
+            np.save(os.path.join(out_dir, f"{prefix}{name}_index.npy"), idx.astype(np.float64))
 
 
 def host_cpu_share():
@@ -322,14 +369,23 @@ def main():
 
     # The headline (SURVEY 8e / BASELINE.json "1e9 x 9-bit column, 1/2/4/8 GPU") is ONE column of --rows rows in N
     # row-range shards: strong scaling.  The weak figure (every rank its own --rows rows) is measured in the same run and
-    # printed beside it; at N = 1 the two partitions are the same measurement.  --scaling weak swaps which one is `value`.
+    # printed beside it under --full; at N = 1 the two partitions are the same measurement.  --scaling weak swaps which
+    # one is `value`.
     phases = {args.scaling: run_phase(args.scaling)}
     other = "weak" if args.scaling == "strong" else "strong"
-    if world > 1:
-        phases[other] = run_phase(other)
-    else:
+    if world == 1:
         phases[other] = phases[args.scaling]
+    elif args.full:
+        phases[other] = run_phase(other)
     ph = phases[args.scaling]
+    if args.dump_outputs:
+        if args.workload == "decompress":
+            outs = [("values", ph["bitmap"][:ph["n"]])]
+        elif args.workload == "shared_scan":
+            outs = [("bitmap", ph["bitmap"][:, :ph["nb"]] if args.layout == "per_predicate" else ph["bitmap"]), ("hits", ph["hits"])]
+        else:
+            outs = [("bitmap", ph["bitmap"][:ph["nb"]]), ("hits", ph["hits"])]
+        dump_outputs(args.dump_outputs, outs, prefix=f"rank{rank}_" if world > 1 else "")
     n, nb, first, total_rows = ph["n"], ph["nb"], ph["first"], ph["total_rows"]
     col, bitmap, hits, expect_hits = ph["col"], ph["bitmap"], ph["hits"], ph["expect_hits"]
     elapsed, dev_ms, algo_bytes, kname, tuned = ph["elapsed"], ph["dev_ms"], ph["algo_bytes"], ph["kname"], ph["tuned"]
@@ -343,7 +399,7 @@ def main():
         """the exchange step, timed apart from the scan; runs in a helper thread so that a bootstrap or collective that
         never returns (a mis-configured fabric) is SEEN: the scan line is still printed, then the rank exits non-zero"""
         torch.cuda.set_device(local_rank)
-        if world > 1 and not args.no_gather and args.workload in ("scan_eq", "scan_range"):
+        if world > 1 and args.full and not args.no_gather and args.workload in ("scan_eq", "scan_range"):
             # final exchange step of the north star: per-shard bitmaps -> rank 0 over xGMI, through the C ABI's RCCL entry
             # points (mi355_comm_create / mi355_gather_bitmaps_dev / mi355_allreduce_hits_dev); a gloo group (rehearsal on a
             # box with fewer GPUs than ranks) uses the torch.distributed transport instead
@@ -446,12 +502,7 @@ def main():
                                    + (f"keys=0..7, layout={args.layout}" if args.workload == "shared_scan" else f"key={key}"),
                        "rows_total": total_rows, "rows_per_gpu": [b - a for a, b in ranges], "bits": c,
                        "parallelism": f"row-range shards x{world}", "tuned_blocks_per_cu": tuned or None},
-            # both partitions, measured in this one run (identical at N = 1): the driver's scaling curve can use either
-            "strong_values_per_s": phases["strong"]["value"], "weak_values_per_s": phases["weak"]["value"],
-            "strong_ms_per_step": phases["strong"]["elapsed"] / args.steps * 1e3,
-            "weak_ms_per_step": phases["weak"]["elapsed"] / args.steps * 1e3,
             "per_rank_kernel_ms": ph["per_rank_ms"],
-            "weak_per_rank_kernel_ms": phases["weak"]["per_rank_ms"], "strong_per_rank_kernel_ms": phases["strong"]["per_rank_ms"],
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": kname, "kernel_ms": dev_ms, "algorithmic_bytes": algo_bytes, "rows_per_launch": n,
@@ -461,7 +512,14 @@ def main():
             "achieved_hbm_gb_per_s": sum((b - a) * (algo_bytes / max(n, 1)) for a, b in ranges) / (max(ph["per_rank_ms"]) * 1e-3) / 1e9,
             "hits": int(hits.sum().item()) if hits is not None else None,
         }
-        if world > 1:
+        # the partitions measured in this run (both at N = 1, where they are one measurement, and at N > 1 under --full):
+        # the driver's scaling curve can use either
+        for s in ("strong", "weak"):
+            if s in phases:
+                line[f"{s}_values_per_s"] = phases[s]["value"]
+                line[f"{s}_ms_per_step"] = phases[s]["elapsed"] / args.steps * 1e3
+                line[f"{s}_per_rank_kernel_ms"] = phases[s]["per_rank_ms"]
+        if world > 1 and args.full:
             line["ranks_seen"] = xr["ranks_seen"]
             line["comm_world"] = xr["comm_world"]
         if gather_via is not None:
@@ -474,7 +532,7 @@ def main():
             line["pipelined_scan_gather_ms"] = pipelined_ms
         if gather_error is not None:
             line["gather_error"] = gather_error
-        if world == 1 and not args.no_cpu_baseline and args.workload == "scan_eq":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "scan_eq":
             line["cpu_baseline"] = cpu_baseline(args, col, bitmap, key)
         print(json.dumps(line), flush=True)
     # A failed or stuck exchange is a FAILURE of the run: the scan line above is complete and printed, and the driver

@@ -97,6 +97,36 @@ def main():
         d[v] = b
         d[v + "_hits"] = np.int32(h)
     np.savez_compressed(os.path.join(here, "ref_tail_w9.npz"), **d)
+    cfg1(O, here)
+
+
+def digest(a, dtype):
+    """sha256 of an array's elements as `dtype` (little-endian, C order) -> uint8[32]"""
+    import hashlib
+
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a, dtype=dtype).tobytes()).digest(), dtype=np.uint8)
+
+
+CFG1_SCANS = ("scan_256_unrolled", "scan_256", "scan_128_unrolled", "scan_128", "scan_unvectorized")
+
+
+def cfg1(O, here):
+    """BASELINE config 1 (n = 1e7, c = 9, v = i % 5, key 3; v = i % 8 and keys 0..7 for the shared scan): the reference's
+    outputs on the whole column, recorded as hit counts and sha256 digests (the buffers themselves are megabytes)"""
+    R = RefLib(9)
+    n, c = 10_000_000, 9
+    vals = O.gen_values("mod", n, c, 5)
+    packed = R.compress(vals.astype(np.uint16))
+    d = {"n": np.int64(n), "width": np.int32(c), "key": np.int32(3), "packed_sha256": digest(packed, np.uint8)}
+    for v in CFG1_SCANS:
+        buf, hits = R.scan(v, 3, packed, n)
+        d[v + "_sha256"] = digest(buf[: n // 8], np.uint8)
+        d[v + "_hits"] = np.int64(hits)
+    d["decompress_256_avx2_sha256"] = digest(R.decompress("decompress_256_avx2", packed, n)[:n], np.int64)
+    packed8 = R.compress(O.gen_values("mod", n, c, 8).astype(np.uint16))
+    d["shared_scan_128_standard_sha256"] = digest(R.shared_scan("shared_scan_128_standard", list(range(8)), packed8, n)[:, : n // 8],
+                                                  np.uint8)
+    np.savez_compressed(os.path.join(here, "ref_cfg1_1e7.npz"), **d)
 
 
 if __name__ == "__main__":

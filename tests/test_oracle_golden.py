@@ -231,32 +231,43 @@ def test_generators_match_reference_bench_inputs(O):
 
 
 def test_cfg1_reference_vs_oracle_1e7(O):
-    """BASELINE config 1 (n = 1e7, c = 9, v = i % 5, key 3; src/benchmark.cpp:173,:150): when the reference itself is
-    available (oracle/_ref, built from /root/reference by oracle/Makefile) run its AVX2 and scalar scans and hold the
-    oracle against them on the full column; hits must be 2,000,000."""
+    """BASELINE config 1 (n = 1e7, c = 9, v = i % 5, key 3; src/benchmark.cpp:173,:150): the oracle on the full column
+    against the reference's AVX2 and scalar scans, its AVX2 decompression and its shared scan (v = i % 8, keys 0..7):
+    against their outputs recorded in tests/golden/ref_cfg1_1e7.npz (hit counts, sha256 of the whole buffers), and
+    against the reference itself when it is available (oracle/_ref, built by oracle/Makefile); hits must be 2,000,000."""
+    from golden.make_golden import CFG1_SCANS, digest
     from oracle import RefLib, ref_available
 
-    if not ref_available(9):
-        pytest.skip("oracle/_ref/libref_w9.so not built (needs /root/reference)")
-    R = RefLib(9)
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cfg1_1e7.npz"))
     n, c = 10_000_000, 9
+    assert int(rec["n"]) == n and int(rec["width"]) == c and int(rec["key"]) == 3
     vals = O.gen_values("mod", n, c, 5)
     packed = O.pack(vals, c)
-    assert np.array_equal(packed, R.compress(vals.astype(np.uint16)))
+    assert np.array_equal(digest(packed, np.uint8), rec["packed_sha256"])
     obm, ohits = O.scan_eq(packed, n, c, 3)
     assert ohits == 2_000_000
-    for variant in ("scan_256_unrolled", "scan_256", "scan_128_unrolled", "scan_128", "scan_unvectorized"):
-        rbuf, rhits = R.scan(variant, 3, packed, n)
-        assert rhits == 2_000_000, variant
-        assert np.array_equal(rbuf[: n // 8], obm), variant  # n is a multiple of 32: whole-buffer equality
-    dec = R.decompress("decompress_256_avx2", packed, n)[:n]
-    assert np.array_equal(dec, O.decompress(packed, n, c))
+    for variant in CFG1_SCANS:
+        assert int(rec[variant + "_hits"]) == 2_000_000, variant
+        assert np.array_equal(digest(obm, np.uint8), rec[variant + "_sha256"]), variant  # n is a multiple of 32
+    dec = O.decompress(packed, n, c)
+    assert np.array_equal(digest(dec, np.int64), rec["decompress_256_avx2_sha256"])
     keys = list(range(8))
     vals8 = O.gen_values("mod", n, c, 8)
     packed8 = O.pack(vals8, c)
-    ref = R.shared_scan("shared_scan_128_standard", keys, packed8, n)
     mine, hits = O.shared_scan_eq(packed8, n, c, keys)
-    assert np.array_equal(ref[:, : n // 8], mine) and hits.tolist() == [n // 8] * 8
+    assert np.array_equal(digest(mine, np.uint8), rec["shared_scan_128_standard_sha256"]) and hits.tolist() == [n // 8] * 8
+
+    if not ref_available(9):
+        return  # the recorded outputs above stand for the reference
+    R = RefLib(9)
+    assert np.array_equal(packed, R.compress(vals.astype(np.uint16)))
+    for variant in CFG1_SCANS:
+        rbuf, rhits = R.scan(variant, 3, packed, n)
+        assert rhits == 2_000_000, variant
+        assert np.array_equal(rbuf[: n // 8], obm), variant  # n is a multiple of 32: whole-buffer equality
+    assert np.array_equal(R.decompress("decompress_256_avx2", packed, n)[:n], dec)
+    ref = R.shared_scan("shared_scan_128_standard", keys, packed8, n)
+    assert np.array_equal(ref[:, : n // 8], mine)
 
 
 def test_committed_fixtures_are_what_the_reference_produces(tmp_path):

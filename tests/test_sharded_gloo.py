@@ -303,8 +303,9 @@ def _bench_2ranks(extra_env, extra_args=()):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_BACKEND="gloo", **extra_env)
     env.pop("WORLD_SIZE", None)
+    # --full: the weak partition and the exchange step are not part of a plain run
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "40000000", "--steps", "5",
-                          "--warmup", "2", *extra_args], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+                          "--warmup", "2", "--full", *extra_args], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     return res, (json.loads(lines[-1]) if lines else None)
 

@@ -91,7 +91,10 @@ MI355_API int mi355_ctx_set_stream(mi355_ctx *ctx, void *hip_stream);
  * "scan_nt_stores" (result stores of the scans: -1 chosen by output size (default: write-through while the bitmap fits
  * the Infinity Cache, non-temporal beyond), 0 plain, 1 non-temporal, 2 write-through), "select_kernel" (mi355_scan_select_dev:
  * 0 / 2 = decoder / expander roles (default), 1 = the older single-role kernel, kept for A/B runs), "kernel_flags" (A/B switches of the kernels; results never depend on them except the two timing
- * ablations of the selection documented in DESIGN.md) */
+ * ablations of the selection documented in DESIGN.md), "grid_cus" (0 = the device's CU count (default); 1 .. CU count: every
+ * persistent grid is sized as if the device had that many CUs -- with "max_blocks_per_cu" = 1 and "grid_cus" = 1 a launch runs
+ * 4 waves, each of which walks thousands of tiles of a large column: the long-loop paths tests need; other values are rejected
+ * with MI355_E_INVALID) */
 MI355_API int mi355_ctx_set_option(mi355_ctx *ctx, const char *name, int value);
 
 /* ---- load-time tuning (optional) ----------------------------------------------------------------------------------
@@ -324,6 +327,14 @@ MI355_API const char *mi355_kernel_name(const char *op, unsigned c);
  * for the 32-keys-per-lookup kernels), "shared_linear_kernel" (linear rows, lanes in memory order), "shared_general_kernel"
  * (tables do not fit in LDS) */
 MI355_API const char *mi355_shared_scan_kernel(mi355_ctx *ctx, unsigned c, unsigned P, int layout, int with_hits);
+/* the kernels the context's most recent compute call launched, in launch order, one line each:
+ *   "<kernel><<template arguments>> grid=<blocks> lds=<dynamic LDS bytes> flags=0x<hex>"
+ * e.g. "shared_wide3_kernel<17, 2, 2, true> grid=512 lds=65536 flags=0x0"; flags is the switch word the kernel received
+ * (ScanArgs::flags, with the bits the launcher sets; 0 for kernels that take none).  Every entry point that may launch
+ * kernels starts a new record (a call made inside another one -- host-pointer flavours, sharded scans -- adds to it); the
+ * options, stream, memory helpers and introspection calls leave it alone.  Host-side text only: recording adds no device work.
+ * The string stays valid until the calling thread calls this function again; NULL when ctx cannot be resolved. */
+MI355_API const char *mi355_ctx_last_launch(mi355_ctx *ctx);
 /* rows per wave tile of the scan kernels at width c (shard boundaries should be multiples of it) */
 MI355_API uint64_t mi355_tile_values(unsigned c);
 

@@ -74,6 +74,7 @@ SYMBOLS = [
     ("mi355_sharded_scan_range_dev", _int, [_vp, _vp, _vp, C.c_uint, _u32, _u32, _vp, _vp, _int, _vp, _vp]),
     ("mi355_kernel_name", C.c_char_p, [C.c_char_p, C.c_uint]),
     ("mi355_shared_scan_kernel", C.c_char_p, [_vp, C.c_uint, C.c_uint, _int, _int]),
+    ("mi355_ctx_last_launch", C.c_char_p, [_vp]),
     ("mi355_tile_values", _u64, [C.c_uint]),
 ]
 

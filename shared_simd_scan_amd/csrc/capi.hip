@@ -120,17 +120,20 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
     if (int rc = bind(ctx)) return rc;
     r.stream = ctx->stream;
     r.device = ctx->device;
-    r.num_cus = ctx->num_cus;
+    r.num_cus = grid_cus(ctx);
+    r.record = &ctx->last_launch;
     r.max_blocks_per_cu = ctx->max_blocks_per_cu;
     r.dma_aux = ctx->dma_aux;
     r.scan_nt_stores = ctx->scan_nt_stores;
     r.shared_vpl = ctx->shared_vpl;
     r.scan_burst = ctx->scan_burst;
-    // the A/B switches of the shared scans (bits 0-8) never reach select_kernel, whose switches live in bits 9-12 of the
-    // option and arrive as its bits 1-4: two TIMING ablations (2 no expansion, 4 no look-back: wrong ids by construction) and
-    // two A/B switches of the chunk hand-out (8 chunks dealt out by block index as in round 2, 16 no barrier per generation)
-    // (option bits 13.. = further switches of the shared scans; they arrive as their bits 9..)
-    r.scan.flags = r.op == kOpSelect ? ((ctx->kernel_flags >> 8) & 0x7eu) : ((ctx->kernel_flags & 0x1ffu) | ((ctx->kernel_flags >> 4) & 0xdfe00u));
+    // the A/B switches of the shared scans (bits 0-8) never reach the selection kernels, whose switches live in bits 9-12 of
+    // the option and arrive as their bits 1-4: two TIMING ablations (2 no expansion, 4 no look-back: wrong ids by construction)
+    // and two A/B switches of select_kernel's chunk hand-out (8 chunks dealt out by block index as in round 2, 16 no barrier
+    // per generation).  Option bits 13.. are further switches of the shared scans; they arrive as their bits 9.. and never reach
+    // the selection.  Option bit 16 (kernel bit 12) is read nowhere and stays out; kernel bits 17 and 20 are the launcher's own.
+    // (tests/test_kernel_paths.py maps every kernel-side test back through these two expressions.)
+    r.scan.flags = r.op == kOpSelect ? ((ctx->kernel_flags >> 8) & 0x1eu) : ((ctx->kernel_flags & 0x1ffu) | ((ctx->kernel_flags >> 4) & 0xdee00u));
     r.scan.scratch = ctx->kernel_scratch;
     if (r.max_blocks_per_cu == 0 && !ctx->tuned_bpc.empty()) {
         const bool scan = r.op == kOpScanEq || r.op == kOpScanRange;
@@ -319,7 +322,10 @@ int mi355_ctx_set_option(mi355_ctx *ctx, const char *name, int value)
         ctx->scan_burst = value;
     else if (!strcmp(name, "kernel_flags"))
         ctx->kernel_flags = (unsigned)value;
-    else
+    else if (!strcmp(name, "grid_cus")) {
+        if (value < 0 || value > ctx->num_cus) return fail(MI355_E_INVALID, "grid_cus=%d outside 0..%d", value, ctx->num_cus);
+        ctx->grid_cus = value;
+    } else
         return fail(MI355_E_INVALID, "unknown option %s", name);
     return MI355_OK;
 }
@@ -400,26 +406,27 @@ static int pack_launch(mi355_ctx *ctx, int src, const void *values_dev, uint64_t
     a.out_dwords = mi355_compressed_buffer_size(c, n) / 4; // payload + pad, whole dwords
     a.c = c;
     uint64_t blocks = (a.out_dwords + 255) / 256;
-    uint64_t cap = (uint64_t)ctx->num_cus * 8;
+    uint64_t cap = (uint64_t)grid_cus(ctx) * 8;
     unsigned grid = (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
+    std::string *const rec = &ctx->last_launch;
     switch (src) {
 #define PACK_BY_WIDTH(SRC)                                                                                          \
     do { /* values per output dword: at most floor(31/c) + 2; one block per 8192-value tile, 4 resident per CU */  \
         uint64_t tiles = (n + kPackTile - 1) / kPackTile;                                                           \
-        uint64_t tcap = (uint64_t)ctx->num_cus * 4;                                                                 \
+        uint64_t tcap = (uint64_t)grid_cus(ctx) * 4;                                                                \
         unsigned tgrid = (unsigned)(tiles < tcap ? (tiles ? tiles : 1) : tcap);                                     \
-        if (c >= 16) hipLaunchKernelGGL((pack_tiled_kernel<SRC, 3>), dim3(tgrid), dim3(256), 0, ctx->stream, a);    \
-        else if (c >= 8) hipLaunchKernelGGL((pack_tiled_kernel<SRC, 5>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
-        else if (c >= 4) hipLaunchKernelGGL((pack_tiled_kernel<SRC, 9>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
-        else if (c >= 2) hipLaunchKernelGGL((pack_tiled_kernel<SRC, 17>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
-        else hipLaunchKernelGGL((pack_tiled_kernel<SRC, 32>), dim3(tgrid), dim3(256), 0, ctx->stream, a);           \
+        if (c >= 16) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 3>), dim3(tgrid), dim3(256), 0, ctx->stream, a);    \
+        else if (c >= 8) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 5>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
+        else if (c >= 4) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 9>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
+        else if (c >= 2) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 17>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
+        else MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 32>), dim3(tgrid), dim3(256), 0, ctx->stream, a);           \
     } while (0)
     case kSrcU16: PACK_BY_WIDTH(kSrcU16); break;
     case kSrcU32: PACK_BY_WIDTH(kSrcU32); break;
 #undef PACK_BY_WIDTH
-    case kSrcMod: hipLaunchKernelGGL(pack_kernel<kSrcMod>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
-    case kSrcSplitmix: hipLaunchKernelGGL(pack_kernel<kSrcSplitmix>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
-    case kSrcIndex: hipLaunchKernelGGL(pack_kernel<kSrcIndex>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
+    case kSrcMod: MI355_LAUNCH(rec, 0, pack_kernel<kSrcMod>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
+    case kSrcSplitmix: MI355_LAUNCH(rec, 0, pack_kernel<kSrcSplitmix>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
+    case kSrcIndex: MI355_LAUNCH(rec, 0, pack_kernel<kSrcIndex>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
     default: return fail(MI355_E_INVALID, "unknown pack source %d", src);
     }
     HIP_TRY(hipGetLastError());
@@ -434,6 +441,7 @@ int mi355_pack_u16_dev(mi355_ctx *ctx, const uint16_t *values_dev, uint64_t n, u
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     return pack_launch(ctx, kSrcU16, values_dev, n, 0, 0, c, packed_dev);
 }
 int mi355_pack_u32_dev(mi355_ctx *ctx, const uint32_t *values_dev, uint64_t n, unsigned c, void *packed_dev)
@@ -441,6 +449,7 @@ int mi355_pack_u32_dev(mi355_ctx *ctx, const uint32_t *values_dev, uint64_t n, u
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     return pack_launch(ctx, kSrcU32, values_dev, n, 0, 0, c, packed_dev);
 }
 int mi355_generate_dev(mi355_ctx *ctx, int kind, uint64_t first_row, uint64_t n, unsigned c, uint64_t param,
@@ -449,6 +458,7 @@ int mi355_generate_dev(mi355_ctx *ctx, int kind, uint64_t first_row, uint64_t n,
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     int src = kind == MI355_GEN_MOD ? kSrcMod : kind == MI355_GEN_SPLITMIX ? kSrcSplitmix : kind == MI355_GEN_INDEX ? kSrcIndex : -1;
     if (src < 0) return fail(MI355_E_INVALID, "unknown generator kind %d", kind);
     return pack_launch(ctx, src, nullptr, n, first_row, param, c, packed_dev);
@@ -459,6 +469,7 @@ static int pack_host(mi355_ctx *ctx, int src, const void *values, size_t elem, u
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (!packed_host || (!values && n)) return fail(MI355_E_INVALID, "null pointer");
     if ((rc = bind(ctx))) return rc;
@@ -487,6 +498,7 @@ int mi355_decompress_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, uns
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (n == 0) return MI355_OK;
     if (!packed_dev || !out_dev) return fail(MI355_E_INVALID, "null device pointer");
@@ -533,6 +545,7 @@ int mi355_scan_eq_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     return scan_common_dev(ctx, kOpScanEq, packed_dev, n, c, (uint32_t)key, 0, bitmap_dev, hits_dev);
 }
 
@@ -542,6 +555,7 @@ int mi355_scan_range_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, uns
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if (lo > hi) {
         // empty range: all-zero bitmap, zero hits
         if ((rc = check_width(c))) return rc;
@@ -559,6 +573,7 @@ int mi355_shared_scan_eq_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n,
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (P < 1 || P > (unsigned)kMaxKeys) return fail(MI355_E_INVALID, "P=%u outside 1..%u", P, kMaxKeys);
     if (!keys_host) return fail(MI355_E_INVALID, "keys is null");
@@ -640,6 +655,7 @@ int mi355_scan_combine_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, u
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (op < MI355_CMP_EQ || op > MI355_CMP_NOT_BETWEEN) return fail(MI355_E_INVALID, "unknown comparison %d", op);
     if (mask_op < MI355_BITMAP_AND || mask_op > MI355_BITMAP_ANDNOT) return fail(MI355_E_INVALID, "unknown mask op %d", mask_op);
@@ -671,6 +687,7 @@ int mi355_scan_select_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, un
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (op < MI355_CMP_EQ || op > MI355_CMP_NOT_BETWEEN) return fail(MI355_E_INVALID, "unknown comparison %d", op);
     if (mask_op < MI355_BITMAP_AND || mask_op > MI355_BITMAP_ANDNOT) return fail(MI355_E_INVALID, "unknown mask op %d", mask_op);
@@ -728,6 +745,7 @@ int mi355_scan2_dev(mi355_ctx *ctx, const void *packed1_dev, unsigned c1, int op
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c1)) || (rc = check_width(c2))) return rc;
     if (op1 < MI355_CMP_EQ || op1 > MI355_CMP_NOT_BETWEEN || op2 < MI355_CMP_EQ || op2 > MI355_CMP_NOT_BETWEEN)
         return fail(MI355_E_INVALID, "unknown comparison");
@@ -779,6 +797,7 @@ int mi355_scan_in_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (P < 1 || P > (unsigned)kMaxKeys) return fail(MI355_E_INVALID, "P=%u outside 1..%u", P, kMaxKeys);
     if (!keys_host) return fail(MI355_E_INVALID, "keys is null");
@@ -824,17 +843,19 @@ static int bitmap_launch(mi355_ctx *ctx, int op, const void *a, const void *b, v
     // partial counts go to the (all-zero) hit-count replicas of the context scratch, then to count_dev
     g.count = count_dev ? ctx->kernel_scratch : nullptr;
     uint64_t blocks = (g.nbytes / 16 + 255) / 256;
-    unsigned grid = (unsigned)(blocks < (uint64_t)ctx->num_cus * 4 ? (blocks ? blocks : 1) : (uint64_t)ctx->num_cus * 4);
+    const uint64_t cap = (uint64_t)grid_cus(ctx) * 4;
+    unsigned grid = (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
+    std::string *const rec = &ctx->last_launch;
     switch (op) {
-    case kBitAnd: hipLaunchKernelGGL(bitmap_kernel<kBitAnd>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
-    case kBitOr: hipLaunchKernelGGL(bitmap_kernel<kBitOr>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
-    case kBitXor: hipLaunchKernelGGL(bitmap_kernel<kBitXor>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
-    case kBitAndNot: hipLaunchKernelGGL(bitmap_kernel<kBitAndNot>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
-    case kBitCount: hipLaunchKernelGGL(bitmap_kernel<kBitCount>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
+    case kBitAnd: MI355_LAUNCH(rec, 0, bitmap_kernel<kBitAnd>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
+    case kBitOr: MI355_LAUNCH(rec, 0, bitmap_kernel<kBitOr>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
+    case kBitXor: MI355_LAUNCH(rec, 0, bitmap_kernel<kBitXor>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
+    case kBitAndNot: MI355_LAUNCH(rec, 0, bitmap_kernel<kBitAndNot>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
+    case kBitCount: MI355_LAUNCH(rec, 0, bitmap_kernel<kBitCount>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
     default: return fail(MI355_E_INVALID, "unknown bitmap op %d", op);
     }
     if (count_dev)
-        hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->kernel_scratch, (unsigned long long *)count_dev);
+        MI355_LAUNCH(rec, 0, sum_slots_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->kernel_scratch, (unsigned long long *)count_dev);
     HIP_TRY(hipGetLastError());
     return MI355_OK;
 }
@@ -845,6 +866,7 @@ int mi355_bitmap_combine_dev(mi355_ctx *ctx, int op, const void *a_dev, const vo
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if (op < MI355_BITMAP_AND || op > MI355_BITMAP_ANDNOT) return fail(MI355_E_INVALID, "unknown bitmap op %d", op);
     return bitmap_launch(ctx, op, a_dev, b_dev, out_dev, n, count_dev);
 }
@@ -854,6 +876,7 @@ int mi355_bitmap_count_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t n, u
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if (!count_dev) return fail(MI355_E_INVALID, "count_dev is null");
     return bitmap_launch(ctx, kBitCount, bitmap_dev, nullptr, nullptr, n, count_dev);
 }
@@ -864,6 +887,7 @@ int mi355_bitmap_to_rowids_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t 
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = bind(ctx))) return rc;
     if (!count_dev) return fail(MI355_E_INVALID, "count_dev is null");
     if (n == 0) {
@@ -891,10 +915,11 @@ int mi355_bitmap_to_rowids_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t 
     g.rowids = rowids_dev;
     g.capacity = capacity;
     uint64_t blocks = (g.nchunks + 3) / 4;
-    unsigned grid = (unsigned)(blocks < (uint64_t)ctx->num_cus * 8 ? blocks : (uint64_t)ctx->num_cus * 8);
-    hipLaunchKernelGGL(rowid_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
-    hipLaunchKernelGGL(rowid_scan_kernel, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, g);
-    hipLaunchKernelGGL(rowid_write_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
+    unsigned grid = (unsigned)(blocks < (uint64_t)grid_cus(ctx) * 8 ? blocks : (uint64_t)grid_cus(ctx) * 8);
+    std::string *const rec = &ctx->last_launch;
+    MI355_LAUNCH(rec, 0, rowid_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
+    MI355_LAUNCH(rec, 0, rowid_scan_kernel, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, g);
+    MI355_LAUNCH(rec, 0, rowid_write_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(count_dev, g.chunk_counts + g.nchunks, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
     return MI355_OK;
@@ -906,6 +931,7 @@ int mi355_gather_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if ((rc = bind(ctx))) return rc;
     if (!count_dev) return fail(MI355_E_INVALID, "count_dev is null (the number of ids is read on the device)");
@@ -923,8 +949,8 @@ int mi355_gather_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
     g.out = out_dev;
     // the grid is sized for `capacity` (the count is only known on the device); idle blocks leave at once
     const uint64_t blocks = (capacity + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < (uint64_t)ctx->num_cus * 16 ? blocks : (uint64_t)ctx->num_cus * 16);
-    hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
+    const unsigned grid = (unsigned)(blocks < (uint64_t)grid_cus(ctx) * 16 ? blocks : (uint64_t)grid_cus(ctx) * 16);
+    MI355_LAUNCH(&ctx->last_launch, 0, gather_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     return MI355_OK;
 }
@@ -934,6 +960,7 @@ int mi355_aggregate_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if ((rc = bind(ctx))) return rc;
     if (!out_dev) return fail(MI355_E_INVALID, "out_dev is null");
@@ -945,8 +972,8 @@ int mi355_aggregate_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     a.mask = (const uint8_t *)mask_dev;
     a.out = (unsigned long long *)out_dev;
     if (n == 0) {
-        hipLaunchKernelGGL(aggregate_init_kernel, dim3(1), dim3(1), 0, ctx->stream, a.out);
-    } else if (!launch_aggregate_width(c, a, ctx->num_cus, ctx->stream)) {
+        MI355_LAUNCH(&ctx->last_launch, 0, aggregate_init_kernel, dim3(1), dim3(1), 0, ctx->stream, a.out);
+    } else if (!launch_aggregate_width(c, a, grid_cus(ctx), ctx->stream, &ctx->last_launch)) {
         return fail(MI355_E_INVALID, "width %u", c);
     }
     HIP_TRY(hipGetLastError());
@@ -958,6 +985,7 @@ int mi355_histogram_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (c > (unsigned)kHistogramMaxBits) return fail(MI355_E_INVALID, "histogram: widths up to %d bits (2^c counters in LDS), got %u", kHistogramMaxBits, c);
     if ((rc = bind(ctx))) return rc;
@@ -971,7 +999,7 @@ int mi355_histogram_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     a.n = n;
     a.mask = (const uint8_t *)mask_dev;
     a.out = (unsigned long long *)counts_dev;
-    if (!launch_histogram_width(c, a, ctx->num_cus, ctx->stream)) return fail(MI355_E_INVALID, "width %u", c);
+    if (!launch_histogram_width(c, a, grid_cus(ctx), ctx->stream, &ctx->last_launch)) return fail(MI355_E_INVALID, "width %u", c);
     HIP_TRY(hipGetLastError());
     return MI355_OK;
 }
@@ -1001,6 +1029,7 @@ int mi355_tune_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned 
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (!packed_dev || ((uintptr_t)packed_dev & 15)) return fail(MI355_E_INVALID, "packed_dev must be a 16-byte aligned device pointer");
     if (what == 0 || (what & ~(unsigned)MI355_TUNE_ALL)) return fail(MI355_E_INVALID, "what=%u: a mask of MI355_TUNE_* bits", what);
@@ -1091,6 +1120,7 @@ int mi355_decompress(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsign
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (n == 0) return MI355_OK;
     if (!packed_host || !out_host) return fail(MI355_E_INVALID, "null pointer");
@@ -1110,6 +1140,7 @@ static int scan_host(mi355_ctx *ctx, int op, const void *packed_host, uint64_t n
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (hits) *hits = 0;
     if (n == 0) return MI355_OK;
@@ -1147,6 +1178,7 @@ static int shared_host(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsi
     int rc = resolve(ctx);
     if (rc) return rc;
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (P < 1 || P > (unsigned)kMaxKeys) return fail(MI355_E_INVALID, "P=%u outside 1..%u", P, kMaxKeys);
     if (!keys) return fail(MI355_E_INVALID, "keys is null");
@@ -1188,6 +1220,15 @@ int mi355_shared_scan_eq_linear(mi355_ctx *ctx, const void *packed_host, uint64_
 }
 
 /* ---- introspection ---- */
+const char *mi355_ctx_last_launch(mi355_ctx *ctx)
+{
+    static thread_local std::string copy;
+    if (resolve(ctx) != MI355_OK) return nullptr;
+    CtxLock lk(ctx->mu);
+    copy = ctx->last_launch;
+    return copy.c_str();
+}
+
 const char *mi355_kernel_name(const char *op, unsigned c)
 {
     static thread_local char buf[96];

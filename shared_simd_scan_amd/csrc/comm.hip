@@ -190,6 +190,7 @@ int mi355_gather_bitmaps_at_dev(mi355_ctx *ctx, mi355_comm *comm, const void *lo
     Rccl *R = rccl();
     if (!R->handle) return fail(MI355_E_COMM, "%s", R->why.c_str());
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = bind(ctx))) return rc;
     if (comm->rank != root) {
         if (mine) RCCL_TRY(R, R->Send(local_dev, (size_t)mine, ncclUint8, root, comm->comm, ctx->stream));
@@ -236,6 +237,7 @@ int mi355_allreduce_hits_dev(mi355_ctx *ctx, mi355_comm *comm, uint64_t *hits_de
     if (count == 0) return MI355_OK;
     Rccl *R = rccl();
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = bind(ctx))) return rc;
     RCCL_TRY(R, R->AllReduce(hits_dev, hits_dev, count, ncclUint64, ncclSum, comm->comm, ctx->stream));
     return MI355_OK;
@@ -267,6 +269,7 @@ int mi355_sharded_scan_eq_dev(mi355_ctx *ctx, mi355_comm *comm, const void *pack
     if (rc) return rc;
     if (!comm || !rows_per_rank) return fail(MI355_E_INVALID, "null pointer");
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = mi355_scan_eq_dev(ctx, packed_dev, rows_per_rank[comm->rank], c, key, local_bitmap_dev, hits_dev))) return rc;
     return sharded_finish(ctx, comm, local_bitmap_dev, rows_per_rank, root, full_bitmap_dev, hits_dev);
 }
@@ -279,6 +282,7 @@ int mi355_sharded_scan_range_dev(mi355_ctx *ctx, mi355_comm *comm, const void *p
     if (rc) return rc;
     if (!comm || !rows_per_rank) return fail(MI355_E_INVALID, "null pointer");
     CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
     if ((rc = mi355_scan_range_dev(ctx, packed_dev, rows_per_rank[comm->rank], c, lo, hi, local_bitmap_dev, hits_dev))) return rc;
     return sharded_finish(ctx, comm, local_bitmap_dev, rows_per_rank, root, full_bitmap_dev, hits_dev);
 }

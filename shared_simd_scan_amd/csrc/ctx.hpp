@@ -19,7 +19,8 @@ struct mi355_ctx {
     int max_blocks_per_cu = 0;
     int scan_nt_stores = -1; // -1: by bitmap size (see width_group.hip), 0 plain, 1 non-temporal
     int shared_vpl = 0;  // 0: engine's choice
-    int select_kernel = 0; // mi355_scan_select_dev: 0 = by the predicate's expected selectivity, 1 = single-role kernel, 2 = decoder / expander roles
+    int select_kernel = 0; // mi355_scan_select_dev: 1 = the older single-role kernel (A/B); 0 and 2 = decoder / expander roles (select2_kernel)
+    int grid_cus = 0;      // persistent grids sized as if the device had this many CUs (tests: long per-wave loops); 0 = num_cus
     unsigned kernel_flags = 0; // experiment switches handed to the kernels (ScanArgs::flags)
     // mi355_tune_dev: blocks per CU measured on THIS device for the large streaming launches; key = tune_key() in capi.hip
     std::map<uint32_t, int> tuned_bpc;
@@ -48,6 +49,10 @@ struct mi355_ctx {
     void *pool[kPoolSlots] = {};
     size_t pool_bytes[kPoolSlots] = {};
     bool is_thread_default = false;
+    // mi355_ctx_last_launch: the kernels the most recent compute entry point launched (dispatch.hpp note_launch), cleared when
+    // the outermost such call starts (host-pointer flavours and compound calls nest)
+    std::string last_launch;
+    int call_depth = 0;
 };
 
 namespace mi355 {
@@ -70,5 +75,20 @@ int bind(mi355_ctx *ctx);
 int pool_get(mi355_ctx *ctx, int slot, size_t bytes, void **out);
 
 typedef std::lock_guard<std::recursive_mutex> CtxLock;
+
+// a compute entry point in progress, taken after the context's lock: the outermost one starts a new launch record
+struct CallScope {
+    mi355_ctx *ctx;
+    explicit CallScope(mi355_ctx *c) : ctx(c)
+    {
+        if (ctx->call_depth++ == 0) ctx->last_launch.clear();
+    }
+    ~CallScope() { ctx->call_depth--; }
+    CallScope(const CallScope &) = delete;
+    CallScope &operator=(const CallScope &) = delete;
+};
+
+// CUs the persistent grids are sized for (option "grid_cus")
+inline int grid_cus(const mi355_ctx *ctx) { return ctx->grid_cus > 0 ? ctx->grid_cus : ctx->num_cus; }
 
 } // namespace mi355

@@ -4,9 +4,71 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdio>
+#include <cstdlib>
+#include <cxxabi.h>
+#include <string>
+#include <type_traits>
+#include <typeinfo>
+
 #include "kernels.hpp"
 
 namespace mi355 {
+
+// ---- launch record (mi355_ctx_last_launch): one line per kernel a call launched, in launch order,
+//   "<name><<template args>> grid=<blocks> lds=<dynamic LDS bytes> flags=0x<ScanArgs::flags>"
+// Host-side text only: no device work, no synchronisation.  The caller holds the context's lock.
+
+// "shared_wide3_kernel<17, 2, 2, true>" out of the demangled type std::integral_constant<void (*)(mi355::ScanArgs),
+// &(void mi355::shared_wide3_kernel<17, 2, 2, true>(mi355::ScanArgs))> (a plain kernel: "..., &mi355::sum_slots_kernel>")
+inline std::string kernel_label_from(const char *demangled)
+{
+    std::string s = demangled ? demangled : "";
+    const size_t at = s.find(", &");
+    if (at == std::string::npos) return s;
+    std::string t = s.substr(at + 3, s.size() - at - 4); // without the closing '>' of integral_constant
+    if (!t.empty() && t[0] == '(') t = t.substr(1, t.size() - 2);
+    if (t.compare(0, 5, "void ") == 0) t = t.substr(5);
+    int depth = 0;
+    for (size_t i = 0; i < t.size(); i++) { // the parameter list starts at the first '(' outside the template arguments
+        if (t[i] == '<') depth++;
+        else if (t[i] == '>') depth--;
+        else if (t[i] == '(' && depth == 0) {
+            t.resize(i);
+            break;
+        }
+    }
+    for (size_t q; (q = t.find("mi355::")) != std::string::npos;) t.erase(q, 7);
+    return t;
+}
+
+template <auto Kernel> const std::string &kernel_label()
+{
+    static const std::string label = [] {
+        int status = 0;
+        char *d = abi::__cxa_demangle(typeid(std::integral_constant<decltype(Kernel), Kernel>).name(), nullptr, nullptr, &status);
+        std::string s = kernel_label_from(d);
+        std::free(d);
+        return s;
+    }();
+    return label;
+}
+
+inline void note_launch(std::string *rec, const std::string &label, const dim3 &grid, size_t lds, uint32_t flags)
+{
+    if (!rec) return;
+    char tail[96];
+    snprintf(tail, sizeof tail, " grid=%u lds=%zu flags=0x%x\n", grid.x * grid.y * grid.z, lds, flags);
+    *rec += label;
+    *rec += tail;
+}
+
+// hipLaunchKernelGGL + the launch record.  FLAGS: the ScanArgs::flags word the kernel receives (0 for kernels without one).
+#define MI355_LAUNCH(REC, FLAGS, KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                                      \
+    do {                                                                                                                   \
+        ::mi355::note_launch((REC), ::mi355::kernel_label<KERNEL>(), dim3(GRID), (size_t)(LDS), (uint32_t)(FLAGS));       \
+        hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                                                 \
+    } while (0)
 
 enum Op { kOpScanEq = 0, kOpScanRange = 1, kOpSharedScan = 2, kOpDecompress = 3, kOpScanIn = 4, kOpSelect = 5, kOpScan2 = 6 };
 
@@ -22,6 +84,7 @@ struct LaunchReq {
     int scan_burst;        // eq / range scan: 0 = tiles per store burst chosen by width (burst_k), 1 = one tile per burst
     int select_single;     // kOpSelect: 1 = the older single-role kernel (option "select_kernel" = 1, A/B), 0 = decoder / expander roles
     int shared_vpl;        // shared scans of <= 8 keys: values per lane and tile, 0 = the engine's choice, 64, 128 (c <= 12)
+    std::string *record;   // the context's launch record (mi355_ctx_last_launch), null = not recorded
     int *choice_out;       // kOpSharedScan: non-null = only report the kernel family that would run (0 one-pass LUT,
                            // 1 byte-entry multi-pass LUT, 2 dword-entry LUT, 3 compare chain), launch nothing
     ScanArgs scan;

@@ -4,6 +4,7 @@
 // one of the profiled hot-path kernels; included by capi.hip only.
 #pragma once
 
+#include "../dispatch.hpp"
 #include "../kernels.hpp"
 
 namespace mi355 {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(kBlockThreads) void aggregate_kernel(AggArgs a)
     }
 }
 
-template <int C> inline void launch_aggregate(const AggArgs &a, int num_cus, hipStream_t stream)
+template <int C> inline void launch_aggregate(const AggArgs &a, int num_cus, hipStream_t stream, std::string *rec)
 {
     constexpr int VPL = scan_vpl(C, kModeEq);
     using G = ScanGeom<C, VPL>;
@@ -155,14 +156,14 @@ template <int C> inline void launch_aggregate(const AggArgs &a, int num_cus, hip
     const uint64_t blocks_wanted = (uint64_t)num_cus * (G::TILE_BYTES < 6144 ? 2 : 1);
     const uint64_t blocks_needed = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned grid = (unsigned)(blocks_needed < blocks_wanted ? (blocks_needed ? blocks_needed : 1) : blocks_wanted);
-    hipLaunchKernelGGL(aggregate_init_kernel, dim3(1), dim3(1), 0, stream, a.out);
-    hipLaunchKernelGGL((aggregate_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    MI355_LAUNCH(rec, 0, aggregate_init_kernel, dim3(1), dim3(1), 0, stream, a.out);
+    MI355_LAUNCH(rec, 0, (aggregate_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
 }
 
-inline bool launch_aggregate_width(unsigned c, const AggArgs &a, int num_cus, hipStream_t stream)
+inline bool launch_aggregate_width(unsigned c, const AggArgs &a, int num_cus, hipStream_t stream, std::string *rec)
 {
     switch (c) {
-#define MI355_AGG_CASE(W) case W: launch_aggregate<W>(a, num_cus, stream); return true;
+#define MI355_AGG_CASE(W) case W: launch_aggregate<W>(a, num_cus, stream, rec); return true;
         MI355_AGG_CASE(1) MI355_AGG_CASE(2) MI355_AGG_CASE(3) MI355_AGG_CASE(4) MI355_AGG_CASE(5) MI355_AGG_CASE(6) MI355_AGG_CASE(7) MI355_AGG_CASE(8)
         MI355_AGG_CASE(9) MI355_AGG_CASE(10) MI355_AGG_CASE(11) MI355_AGG_CASE(12) MI355_AGG_CASE(13) MI355_AGG_CASE(14) MI355_AGG_CASE(15) MI355_AGG_CASE(16)
         MI355_AGG_CASE(17) MI355_AGG_CASE(18) MI355_AGG_CASE(19) MI355_AGG_CASE(20) MI355_AGG_CASE(21) MI355_AGG_CASE(22) MI355_AGG_CASE(23) MI355_AGG_CASE(24)

@@ -4,6 +4,7 @@
 // counter and block at the end.  Built from the scan's tile pipeline; included by capi.hip only.
 #pragma once
 
+#include "../dispatch.hpp"
 #include "../kernels.hpp"
 
 namespace mi355 {
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(kBlockThreads) void histogram_kernel(HistArgs a)
     }
 }
 
-template <int C> inline void launch_histogram(const HistArgs &a, int num_cus, hipStream_t stream)
+template <int C> inline void launch_histogram(const HistArgs &a, int num_cus, hipStream_t stream, std::string *rec)
 {
     constexpr int VPL = 128;
     using G = ScanGeom<C, VPL>;
@@ -110,13 +111,13 @@ template <int C> inline void launch_histogram(const HistArgs &a, int num_cus, hi
     const uint64_t blocks_wanted = (uint64_t)num_cus * (two ? 2 : 1);
     const uint64_t blocks_needed = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned grid = (unsigned)(blocks_needed < blocks_wanted ? (blocks_needed ? blocks_needed : 1) : blocks_wanted);
-    hipLaunchKernelGGL((histogram_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    MI355_LAUNCH(rec, 0, (histogram_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
 }
 
-inline bool launch_histogram_width(unsigned c, const HistArgs &a, int num_cus, hipStream_t stream)
+inline bool launch_histogram_width(unsigned c, const HistArgs &a, int num_cus, hipStream_t stream, std::string *rec)
 {
     switch (c) {
-#define MI355_HIST_CASE(W) case W: launch_histogram<W>(a, num_cus, stream); return true;
+#define MI355_HIST_CASE(W) case W: launch_histogram<W>(a, num_cus, stream, rec); return true;
         MI355_HIST_CASE(1) MI355_HIST_CASE(2) MI355_HIST_CASE(3) MI355_HIST_CASE(4) MI355_HIST_CASE(5) MI355_HIST_CASE(6) MI355_HIST_CASE(7)
         MI355_HIST_CASE(8) MI355_HIST_CASE(9) MI355_HIST_CASE(10) MI355_HIST_CASE(11) MI355_HIST_CASE(12) MI355_HIST_CASE(13) MI355_HIST_CASE(14)
 #undef MI355_HIST_CASE

@@ -137,7 +137,15 @@ __global__ __launch_bounds__(kSel2Waves * 64, 1) void select2_kernel(ScanArgs a)
     else
         __builtin_amdgcn_s_setprio(0);
     bool gave_up = false;
-    uint32_t dbg_polls = 0, dbg_retries = 0, dbg_tagspins = 0; // (flags bit 6: diagnostics, written behind the count)
+    // Look-back diagnostics (tools/select_debug.py) exist only in a library built with -DMI355_SELECT_DEBUG: they write 512
+    // timestamps behind rowids[capacity] and three counters behind the count word, past the buffers mi355_scan_select_dev
+    // documents, so no option reaches them.
+#ifdef MI355_SELECT_DEBUG
+    constexpr bool kDiag = true;
+#else
+    constexpr bool kDiag = false;
+#endif
+    uint32_t dbg_polls = 0, dbg_retries = 0, dbg_tagspins = 0; // (kDiag: written behind the count)
     // ---- the look-back, one per BLOCK and generation -------------------------------------------------------------------
     // A block's D chunks of a generation are consecutive (one ticket), so the look-back's unit is the block-generation
     // ("super-chunk" base / D): its aggregate leaves with the last of the block's decoders to finish (LDS atomics below), ONE
@@ -319,7 +327,7 @@ __global__ __launch_bounds__(kSel2Waves * 64, 1) void select2_kernel(ScanArgs a)
 
     uint64_t prev_base = ~0ull;
     uint32_t gen = 0;
-    const bool stamps = (a.flags & 64u) && blockIdx.x == 0 && lane == 0; // diagnostics: 8 words per generation behind the ids
+    const bool stamps = kDiag && blockIdx.x == 0 && lane == 0; // diagnostics: 8 words per generation behind the ids
     auto stamp = [&](int slot) {
         if (stamps && gen < 64) a.rowids[a.capacity + gen * 8 + slot] = __builtin_amdgcn_s_memrealtime();
     };
@@ -558,7 +566,7 @@ __global__ __launch_bounds__(kSel2Waves * 64, 1) void select2_kernel(ScanArgs a)
         gen++;
     }
     if (gave_up && lane == 0) __hip_atomic_fetch_max(a.hits, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((a.flags & 64u) && lane == 0 && !decoder) { // diagnostics: the caller's count buffer has 4 words
+    if (kDiag && lane == 0 && !decoder) { // diagnostics: the caller's count buffer has 4 words
         __hip_atomic_fetch_add(a.hits + 1, (unsigned long long)dbg_polls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_add(a.hits + 2, (unsigned long long)dbg_retries, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_add(a.hits + 3, (unsigned long long)dbg_tagspins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -95,13 +95,13 @@ template <int C, int MODE> void launch_scan(const LaunchReq &r)
         static const int bpcK = blocks_per_cu(scan_burst_kernel<C, MODE, 34, VPL, K>);
         const dim3 grid(grid_for((ntiles + K - 1) / K, scan_bpc(bpcK, G::TILE_BYTES, r), r.num_cus));
         if (r.dma_aux == 0)
-            hipLaunchKernelGGL((scan_burst_kernel<C, MODE, 0, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 0, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
         else if (policy == 1)
-            hipLaunchKernelGGL((scan_burst_kernel<C, MODE, 18, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 18, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
         else if (policy == 2)
-            hipLaunchKernelGGL((scan_burst_kernel<C, MODE, 34, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 34, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
         else
-            hipLaunchKernelGGL((scan_burst_kernel<C, MODE, 2, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 2, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
     };
     // "scan_burst" option: 0 = the width's default, 1 = one tile per burst (A/B)
     if (burst_k(C) > 1 && r.scan_burst != 1)
@@ -131,17 +131,17 @@ template <int C, int VPL> void launch_lut8(const LaunchReq &r, uint32_t P, bool 
     // back, P = 8: 1e8 rows sc1 0.046 ms / plain 0.047 / nt 0.049; 1e9 rows nt 0.353-0.383 / sc1 0.347-0.393 / plain 0.40)
     const int spol = r.scan_nt_stores < 0 ? ((r.scan.n / 8) * P > (768ull << 20) ? 1 : 2) : r.scan_nt_stores; // 0 plain, 1 nt, 2 sc1
     if (linear && spol == 1)
-        hipLaunchKernelGGL((shared_lut_kernel<C, 18, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+        MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 18, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
     else if (linear && spol == 2)
-        hipLaunchKernelGGL((shared_lut_kernel<C, 34, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+        MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 34, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
     else if (linear)
-        hipLaunchKernelGGL((shared_lut_kernel<C, 2, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+        MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 2, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
     else if (spol == 1)
-        hipLaunchKernelGGL((shared_lut_kernel<C, 18, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+        MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 18, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
     else if (spol == 2)
-        hipLaunchKernelGGL((shared_lut_kernel<C, 34, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+        MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 34, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
     else
-        hipLaunchKernelGGL((shared_lut_kernel<C, 2, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+        MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 2, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
 }
 
 // which shared scans of <= 8 keys run with 128 values per lane by default (A/B on MI355X: see DESIGN.md section 3.1b)
@@ -229,9 +229,9 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                 // result stores as in launch_lut8: write-through below 768 MiB of output, non-temporal beyond
                 const int spol = r.scan_nt_stores < 0 ? ((r.scan.n / 8) * P > (768ull << 20) ? 1 : 2) : r.scan_nt_stores;
                 if (spol == 1)
-                    hipLaunchKernelGGL((shared_pair_kernel<C, 18, PVPL>), pgrid, dim3(kBlockThreads), 0, r.stream, r.scan);
+                    MI355_LAUNCH(r.record, r.scan.flags, (shared_pair_kernel<C, 18, PVPL>), pgrid, dim3(kBlockThreads), 0, r.stream, r.scan);
                 else
-                    hipLaunchKernelGGL((shared_pair_kernel<C, 34, PVPL>), pgrid, dim3(kBlockThreads), 0, r.stream, r.scan);
+                    MI355_LAUNCH(r.record, r.scan.flags, (shared_pair_kernel<C, 34, PVPL>), pgrid, dim3(kBlockThreads), 0, r.stream, r.scan);
             };
             if (linear)
                 go(std::integral_constant<int, 64>{});
@@ -271,7 +271,7 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                 int fit = (int)((160 * 1024) / (bdyn + fixed));
                 fit = fit > 2 ? 2 : (fit < 1 ? 1 : fit);
                 const dim3 g3(grid_for(ntiles, r.max_blocks_per_cu > 0 && r.max_blocks_per_cu < fit ? r.max_blocks_per_cu : fit, r.num_cus));
-                hipLaunchKernelGGL((shared_linear3_kernel<C, 2, RC, BIG>), g3, dim3(kBlockThreads), bdyn, r.stream, r.scan);
+                MI355_LAUNCH(r.record, r.scan.flags, (shared_linear3_kernel<C, 2, RC, BIG>), g3, dim3(kBlockThreads), bdyn, r.stream, r.scan);
             };
             auto with_big3 = [&](auto rc_c) {
                 if constexpr (kBigWidth) {
@@ -294,8 +294,8 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
             // 0.41 / 0.58 / 0.91 / 1.50 for the dword-entry kernel, which wins from P = 256: 2.80 against 3.16 ms)
             const size_t dyn = ((size_t)((P + 7) / 8) * LutGeom<C, true>::TABLE_BYTES + 15) / 16 * 16;
             allow_dynamic_lds<shared_lut_kernel<C, 2, VPL, 1, true>>((int)(160 * 1024 - lut_static_lds<C, VPL>()), r.device);
-            hipLaunchKernelGGL((shared_lut_kernel<C, 2, VPL, 1, true>), dim3(grid_for(ntiles, lut_bpc(8), r.num_cus)),
-                               dim3(kBlockThreads), dyn, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (shared_lut_kernel<C, 2, VPL, 1, true>), dim3(grid_for(ntiles, lut_bpc(8), r.num_cus)),
+                         dim3(kBlockThreads), dyn, r.stream, r.scan);
         } else if (lut_fits<C, VPL>(P) && !(r.scan.flags & 64u) && !chain_pays) { // one dword-entry lookup table per 32 keys, in dynamic LDS
             // (flags bit 6: the compare chain, for A/B)
             const size_t dyn = (size_t)((P + 31) / 32) * WideLutGeom<C>::TABLE_BYTES;
@@ -315,7 +315,7 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                 // everything else: full tables in memory order, the short last table on its own (shared_linear2_kernel; flags
                 // bit 8: round 2's kernel, which gives the short table a whole lane per row, for A/B)
                 if (P == 16 && C > 10 && !(r.scan.flags & 16u))
-                    hipLaunchKernelGGL((shared_linear_kernel<C, 2, 2>), lgrid, dim3(kBlockThreads), dyn, r.stream, r.scan);
+                    MI355_LAUNCH(r.record, r.scan.flags, (shared_linear_kernel<C, 2, 2>), lgrid, dim3(kBlockThreads), dyn, r.stream, r.scan);
                 // shared_linear2_kernel (the short last table on the full piece's lane / in steps of its own) is the product only for
                 // rows below 32 keys without hit counts (2.5e8 x 9 bit, same box: P = 12: 4.09 against 3.77 TB/s; with hit counts
                 // 2.87 against 3.43).  For rows of 33 .. 63 keys it beat round 2's kernel (P = 33: 3.10 against 2.59) until that kernel
@@ -336,13 +336,13 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                         a1.flags |= 0x100000u;
                         dyn1 += (size_t)kWavesPerBlock * kLinearImageBytes;
                     }
-                    hipLaunchKernelGGL((shared_linear_kernel<C, 2, 1>), lgrid, dim3(kBlockThreads), dyn1, r.stream, a1);
+                    MI355_LAUNCH(r.record, a1.flags, (shared_linear_kernel<C, 2, 1>), lgrid, dim3(kBlockThreads), dyn1, r.stream, a1);
                 }
                 else {
                     ScanArgs a2 = r.scan;
                     if (attach_short(P, r.scan.flags, r.scan.hits != nullptr)) a2.flags |= 0x20000u;
                     allow_dynamic_lds<shared_linear2_kernel<C, 2>>(max_dyn, r.device);
-                    hipLaunchKernelGGL((shared_linear2_kernel<C, 2>), lgrid, dim3(kBlockThreads), dyn, r.stream, a2);
+                    MI355_LAUNCH(r.record, a2.flags, (shared_linear2_kernel<C, 2>), lgrid, dim3(kBlockThreads), dyn, r.stream, a2);
                 }
             } else if (!linear && !(r.scan.flags & 2u)) { // (flags bit 1: the per-group kernel, for A/B)
                 // Hit counts in registers (flags bit 3: per-tile wave reductions / the histogram instead, for A/B): one 32-key
@@ -376,9 +376,9 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                             fit = fit > kWaves ? kWaves : (fit < 1 ? 1 : fit);
                             const dim3 g3(grid_for(ntiles, r.max_blocks_per_cu > 0 && r.max_blocks_per_cu < fit ? r.max_blocks_per_cu : fit, r.num_cus));
                             if (nt_stores)
-                                hipLaunchKernelGGL((shared_wide3_kernel<C, 18, RC, BIG>), g3, dim3(kBlockThreads), bdyn, r.stream, r.scan);
+                                MI355_LAUNCH(r.record, r.scan.flags, (shared_wide3_kernel<C, 18, RC, BIG>), g3, dim3(kBlockThreads), bdyn, r.stream, r.scan);
                             else
-                                hipLaunchKernelGGL((shared_wide3_kernel<C, 2, RC, BIG>), g3, dim3(kBlockThreads), bdyn, r.stream, r.scan);
+                                MI355_LAUNCH(r.record, r.scan.flags, (shared_wide3_kernel<C, 2, RC, BIG>), g3, dim3(kBlockThreads), bdyn, r.stream, r.scan);
                         };
                         auto with_big3 = [&](auto rc_c) {
                             if constexpr (kBigWidth) {
@@ -405,9 +405,9 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                     allow_dynamic_lds<shared_wide2_kernel<C, 2, VPL, RC, BIG>>(max_dyn, r.device);
                     allow_dynamic_lds<shared_wide2_kernel<C, 18, VPL, RC, BIG>>(max_dyn, r.device);
                     if (nt_stores)
-                        hipLaunchKernelGGL((shared_wide2_kernel<C, 18, VPL, RC, BIG>), grid, dim3(kBlockThreads), bdyn, r.stream, r.scan);
+                        MI355_LAUNCH(r.record, r.scan.flags, (shared_wide2_kernel<C, 18, VPL, RC, BIG>), grid, dim3(kBlockThreads), bdyn, r.stream, r.scan);
                     else
-                        hipLaunchKernelGGL((shared_wide2_kernel<C, 2, VPL, RC, BIG>), grid, dim3(kBlockThreads), bdyn, r.stream, r.scan);
+                        MI355_LAUNCH(r.record, r.scan.flags, (shared_wide2_kernel<C, 2, VPL, RC, BIG>), grid, dim3(kBlockThreads), bdyn, r.stream, r.scan);
                 };
                 // (register counters in shared_wide2_kernel only at the single-table widths: the digit-table widths that come here
                 // -- more than 64 keys with hit counts, or the A/B switch -- have no registers to spare for them)
@@ -425,15 +425,15 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
                     go(std::integral_constant<int, 0>{}, std::false_type{});
                 }
             } else if (linear)
-                hipLaunchKernelGGL((shared_wide_kernel<C, 2, VPL, 1>), grid, dim3(kBlockThreads), dyn, r.stream, r.scan);
+                MI355_LAUNCH(r.record, r.scan.flags, (shared_wide_kernel<C, 2, VPL, 1>), grid, dim3(kBlockThreads), dyn, r.stream, r.scan);
             else if (nt_stores)
-                hipLaunchKernelGGL((shared_wide_kernel<C, 18, VPL, 0>), grid, dim3(kBlockThreads), dyn, r.stream, r.scan);
+                MI355_LAUNCH(r.record, r.scan.flags, (shared_wide_kernel<C, 18, VPL, 0>), grid, dim3(kBlockThreads), dyn, r.stream, r.scan);
             else
-                hipLaunchKernelGGL((shared_wide_kernel<C, 2, VPL, 0>), grid, dim3(kBlockThreads), dyn, r.stream, r.scan);
+                MI355_LAUNCH(r.record, r.scan.flags, (shared_wide_kernel<C, 2, VPL, 0>), grid, dim3(kBlockThreads), dyn, r.stream, r.scan);
         } else { // more keys than the tables hold: compare chain, ceil(P/8) passes over the registers
             static const int bpc = blocks_per_cu(shared_general_kernel<C, 2, VPL>);
-            hipLaunchKernelGGL((shared_general_kernel<C, 2, VPL>), dim3(grid_for(ntiles, cap_bpc(bpc, r), r.num_cus)), dim3(kBlockThreads), 0,
-                               r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (shared_general_kernel<C, 2, VPL>), dim3(grid_for(ntiles, cap_bpc(bpc, r), r.num_cus)),
+                         dim3(kBlockThreads), 0, r.stream, r.scan);
         }
         break;
     }
@@ -448,11 +448,11 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
         if (r.max_blocks_per_cu <= 0 && want < 2 && bpc >= 2) want = 2;
         const int ipol = r.scan_nt_stores < 0 ? (r.scan.n / 8 > (768ull << 20) ? 1 : 2) : r.scan_nt_stores; // as in launch_scan
         if (ipol == 2)
-            hipLaunchKernelGGL((in_kernel<C, 34, VPL>), dim3(grid_for(ntiles, want, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (in_kernel<C, 34, VPL>), dim3(grid_for(ntiles, want, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
         else if (ipol == 1)
-            hipLaunchKernelGGL((in_kernel<C, 18, VPL>), dim3(grid_for(ntiles, want, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (in_kernel<C, 18, VPL>), dim3(grid_for(ntiles, want, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
         else
-            hipLaunchKernelGGL((in_kernel<C, 2, VPL>), dim3(grid_for(ntiles, want, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (in_kernel<C, 2, VPL>), dim3(grid_for(ntiles, want, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
         break;
     }
     case kOpSelect: {
@@ -463,11 +463,12 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
         using G = ScanGeom<C, VPL>;
         const uint64_t ntiles = (r.scan.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
         const uint64_t nchunks = (ntiles + select_tiles(C) - 1) / select_tiles(C);
-        // (flags bit 5 = option bit 13: round 2's single-role kernel, for A/B)
-        if ((r.scan.flags & 32u) || r.select_single)
-            hipLaunchKernelGGL((select_kernel<C, kModeRange, VPL>), dim3(grid_for(nchunks, 1, r.num_cus)), dim3(kBlockThreads), 0, r.stream, r.scan);
+        // (option "select_kernel" = 1: round 2's single-role kernel, for A/B)
+        const dim3 sgrid(grid_for(nchunks, 1, r.num_cus));
+        if (r.select_single)
+            MI355_LAUNCH(r.record, r.scan.flags, (select_kernel<C, kModeRange, VPL>), sgrid, dim3(kBlockThreads), 0, r.stream, r.scan);
         else
-            hipLaunchKernelGGL((select2_kernel<C, kModeRange, VPL>), dim3(grid_for(nchunks, 1, r.num_cus)), dim3(kSel2Waves * 64), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (select2_kernel<C, kModeRange, VPL>), sgrid, dim3(kSel2Waves * 64), 0, r.stream, r.scan);
         break;
     }
     case kOpScan2: {
@@ -479,9 +480,9 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
         const dim3 grid(grid_for(ntiles, scan_bpc(bpc, 2 * G::TILE_BYTES, r), r.num_cus));
         const int policy = r.scan_nt_stores < 0 ? (r.scan.n / 8 > (768ull << 20) ? 1 : 2) : r.scan_nt_stores;
         if (policy == 1)
-            hipLaunchKernelGGL((scan2_kernel<C, 18, VPL>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (scan2_kernel<C, 18, VPL>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
         else
-            hipLaunchKernelGGL((scan2_kernel<C, 34, VPL>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, r.scan.flags, (scan2_kernel<C, 34, VPL>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
         break;
     }
     case kOpDecompress: {
@@ -495,13 +496,13 @@ template <int C> hipError_t launch_width(const LaunchReq &r)
         const int want = bpc < 2 ? bpc : 2;
         const unsigned grid = grid_for(ntiles, r.max_blocks_per_cu > 0 ? cap_bpc(bpc, r) : want, r.num_cus);
         if (r.dma_aux == 0)
-            hipLaunchKernelGGL((decompress_kernel<C, 0>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
+            MI355_LAUNCH(r.record, 0, (decompress_kernel<C, 0>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
         else if (r.dma_aux == 2) // nt DMA loads only (tools/sweep.py --aux 2)
-            hipLaunchKernelGGL((decompress_kernel<C, 2>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
+            MI355_LAUNCH(r.record, 0, (decompress_kernel<C, 2>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
         else if (r.dma_aux == 34) // nt loads + write-through stores
-            hipLaunchKernelGGL((decompress_kernel<C, 34>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
+            MI355_LAUNCH(r.record, 0, (decompress_kernel<C, 34>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
         else // default (dma_aux 18): nt loads + nt stores -- the 4 B/value output is written once (+1-2 %)
-            hipLaunchKernelGGL((decompress_kernel<C, 18>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
+            MI355_LAUNCH(r.record, 0, (decompress_kernel<C, 18>), dim3(grid), dim3(kBlockThreads), 0, r.stream, r.decomp);
         break;
     }
     default:

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
-"""tools/select_debug.py -- select2_kernel look-back diagnostics (option kernel_flags bit 14): polls, retries (a nearer chunk had
-not published yet), LDS tag spins of the partner expanders, summed over the launch."""
+"""tools/select_debug.py -- select2_kernel look-back diagnostics: polls, retries (a nearer chunk had not published yet), LDS tag
+spins of the partner expanders, summed over the launch, and a per-generation timeline of block 0.
+
+The diagnostics exist only in a library built with -DMI355_SELECT_DEBUG, where EVERY selection writes them: 512 timestamps behind
+rowids[capacity] and three counters behind the count word.  Build one for this tool only, never for the product:
+    make -C shared_simd_scan_amd/csrc clean && make -C shared_simd_scan_amd/csrc EXTRA_FLAGS=-DMI355_SELECT_DEBUG
+(and rebuild without it afterwards)."""
 import ctypes as C
 import os
 import sys
@@ -14,7 +19,6 @@ from shared_simd_scan_amd._capi import check  # noqa: E402
 eng = ScanEngine(0)
 n, c = 1_000_000_000, 9
 col = eng.generate("splitmix", n, c, 42)
-eng.set_option("kernel_flags", 16384)
 eng.set_option("select_kernel", 2)
 for op, x, cap in ((0, 77, 4_000_000), (2, 8, 20_000_000), (2, 64, 130_000_000), (2, 256, 510_000_000)):  # MI355_CMP_EQ, MI355_CMP_LT
     ids = torch.zeros(cap + 1024, dtype=torch.int64, device="cuda")

@@ -5,7 +5,9 @@ uses the HIP engine); what is under test is the product's sharding logic: row-ra
 hit-count reduction, ragged last shard.
 """
 import os
+import queue
 import socket
+import time
 
 import numpy as np
 import pytest
@@ -20,6 +22,47 @@ def free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def join_or_kill(procs, timeout, q=None):
+    """Wait up to `timeout` seconds in all for the rank processes; a rank that failed ends the wait at once (its peers
+    may be blocked in a collective waiting for it).  Survivors are terminated, then killed, before the test fails: a
+    hung rank must not stay on the GPU.  Returns what the ranks put on `q` meanwhile (drained while waiting, so that no
+    child blocks on a full queue at exit)."""
+    deadline = time.monotonic() + timeout
+    got = []
+
+    def drain():
+        while q is not None:
+            try:
+                got.append(q.get_nowait())
+            except queue.Empty:
+                return
+
+    while any(p.is_alive() for p in procs) and time.monotonic() < deadline:
+        drain()
+        if any(p.exitcode not in (None, 0) for p in procs):
+            break
+        time.sleep(0.1)
+    survivors = [p for p in procs if p.is_alive()]
+    for p in survivors:
+        p.terminate()
+    for p in survivors:
+        p.join(10)
+        if p.is_alive():
+            p.kill()
+            p.join(10)
+    for p in procs:
+        p.join(1)
+    drain()
+    codes = [p.exitcode for p in procs]
+    if any(c != 0 for c in codes):
+        msg = f"rank exit codes {codes}"
+        if survivors:
+            msg += f"; {len(survivors)} rank(s) still running after {timeout} s were terminated"
+        reports = [m for m in got if isinstance(m, str)]  # e.g. a rank's traceback
+        pytest.fail("\n".join([msg] + reports))
+    return got
 
 
 def test_shard_rows_partition():
@@ -141,9 +184,7 @@ def test_sharded_scan_world2_gloo(n):
     procs = [ctx.Process(target=worker, args=(r, world, port, n, c, q)) for r in range(world)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
+    join_or_kill(procs, 240)
     status, ranges = q.get(timeout=10)
     assert status == "ok", ranges
 
@@ -225,9 +266,7 @@ def test_sharded_scan_world2_real_engine(n, c, base_row):
     procs = [ctx.Process(target=gpu_worker, args=(r, world, port, n, c, base_row, q)) for r in range(world)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(300)
-        assert p.exitcode == 0
+    join_or_kill(procs, 600)
     status, ranges = q.get(timeout=10)
     assert status == "ok", ranges
 

@@ -21,8 +21,14 @@
  *   - bitmap format: bit i = byte i/8, bit i%8 (src/util.cpp:51-58).  The engine writes exactly
  *     ceil(n/8) bytes; bits >= n of the last byte are 0; hits = popcount over [0, n).  (The
  *     reference's variants disagree with each other past n; see DESIGN.md "tail rule".)
- *   - keys are signed 32-bit and compared unmasked: a key outside [0, 2^c) matches nothing
- *     (reference behaviour, SURVEY 8c hazard 5).
+ *   - keys are signed 32-bit and compared unmasked as their unsigned 32-bit pattern: below c = 32 a key outside
+ *     [0, 2^c) -- a negative one included -- matches nothing (reference behaviour, SURVEY 8c hazard 5); at c = 32
+ *     every pattern is a value, so key -1 matches 0xffffffff and key INT32_MIN matches 0x80000000.
+ *   - the int64 constants of the comparisons below (mi355_scan_where_dev and its kin) take any value and compare
+ *     exactly against the unsigned decoded value: v < INT64_MIN matches nothing, v <= INT64_MAX every row.
+ *   - aliasing: the only buffers that may be the same memory are the ones a function's comment names (the in-place
+ *     forms: mask and result bitmap of mi355_scan_combine_dev / mi355_scan_where_dev / mi355_scan_in_dev, and the
+ *     operands and result of mi355_bitmap_combine_dev); partial overlap is never allowed.
  *   - *_dev functions take DEVICE pointers, enqueue on the context's stream and return without
  *     synchronising; the others take HOST pointers, copy in/out and return when done.
  *   - a context binds one device and one stream and owns the scratch the kernels use.  Threading contract (the
@@ -198,8 +204,9 @@ MI355_API int mi355_shared_scan_eq_dev(mi355_ctx *ctx, const void *packed_dev, u
 #define MI355_CMP_BETWEEN 6     /* a <= v <= b */
 #define MI355_CMP_NOT_BETWEEN 7 /* v < a or v > b */
 /* bitmap[i] = (v_i OP a [, b]) AND (and_mask_dev ? and_mask[i] : 1).  Unsigned comparison on the decoded value;
- * a, b are clamped to the column's domain [0, 2^c).  and_mask_dev (nullable): a canonical bitmap of
- * >= ceil(n/8) bytes, 16-byte aligned -- chains conjunctions over several columns without a separate AND pass. */
+ * a, b may be any int64 (a constant outside [0, 2^c) compares as what it is: v > -5 holds for every row, v == 2^c for
+ * none).  and_mask_dev (nullable): a canonical bitmap of >= ceil(n/8) bytes, 16-byte aligned -- chains conjunctions over
+ * several columns without a separate AND pass; it may be bitmap_dev itself (in place). */
 MI355_API int mi355_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, int op, int64_t a, int64_t b,
                                    const void *and_mask_dev, void *bitmap_dev, uint64_t *hits_dev);
 /* The general form, fused consumers included (the intent of src/simd_scan.hpp:76-84):
@@ -210,13 +217,14 @@ MI355_API int mi355_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint6
  *                                                                      MI355_BITMAP_ANDNOT  mask & ~p  (rows of mask that fail p)
  * so a chain of predicates over several columns never needs a separate bitmap pass.
  * bitmap_dev == NULL: COUNT-ONLY scan -- only hits_dev is produced, nothing is stored (the kernel then runs at the
- * speed of the read stream alone; `SELECT count(*) WHERE ...`). */
+ * speed of the read stream alone; `SELECT count(*) WHERE ...`).  mask_dev may be bitmap_dev itself: the combination
+ * is then made in place (every wave reads a tile's mask bytes before it stores that tile's result). */
 MI355_API int mi355_scan_combine_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, int op, int64_t a, int64_t b,
                                      int mask_op, const void *mask_dev, void *bitmap_dev, uint64_t *hits_dev);
 
 /* bitmap[i] = (v_i IN {keys[0..P-1]}) AND (and_mask ? and_mask[i] : 1), negated when `negate` != 0 (NOT IN).
- * 1 <= P <= 1024; keys outside [0, 2^c) match nothing.  c <= 16: bitset lookup, cost independent of P;
- * c > 16: compare chain, O(P) per value. */
+ * 1 <= P <= 1024; keys as in mi355_scan_eq_dev (below c = 32, keys outside [0, 2^c) match nothing).  c <= 16: bitset
+ * lookup, cost independent of P; c > 16: compare chain, O(P) per value.  and_mask_dev may be bitmap_dev itself (in place). */
 MI355_API int mi355_scan_in_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, const int32_t *keys_host, unsigned P,
                                 int negate, const void *and_mask_dev, void *bitmap_dev, uint64_t *hits_dev);
 

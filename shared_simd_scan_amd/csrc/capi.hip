@@ -615,10 +615,14 @@ int mi355_shared_scan_eq_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n,
 
 /* ---- predicates and bitmap consumers beyond the reference ---- */
 // every comparison is an inclusive range [lo, hi] over the column's domain [0, 2^c), possibly negated: fills
-// key[0] = lo, key[1] = hi - lo and the negation word of a scan request
+// key[0] = lo, key[1] = hi - lo and the negation word of a scan request.  a and b may be any int64: clamped to
+// [-1, 2^32] first, which changes no comparison with a value in [0, 2^32) and keeps a - 1 / a + 1 from overflowing
 static void fill_predicate(ScanArgs &sa, unsigned c, int op, int64_t a, int64_t b)
 {
     const int64_t vmax = c == 32 ? 0xffffffffll : ((1ll << c) - 1);
+    const int64_t kBelow = -1, kAbove = 1ll << 32;
+    a = a < kBelow ? kBelow : (a > kAbove ? kAbove : a);
+    b = b < kBelow ? kBelow : (b > kAbove ? kAbove : b);
     int64_t lo = 0, hi = vmax;
     bool invert = false, empty = false;
     switch (op) {

@@ -44,6 +44,45 @@ def kernel_name(op: str, c: int) -> str:
     return s.decode()
 
 
+# ---- predicate constants -> C ABI arguments --------------------------------------------------------------------------
+# ctypes masks an int that does not fit the argument's C type without an error (c_uint32(-1) is 0xffffffff, c_int64(2**64 + 5)
+# is 5), so every constant a caller passes goes through one of these first: they give the C side a value of its type that
+# selects exactly the rows the Python int selects, or raise.
+def clamp_const(x: int) -> int:
+    """a comparison constant of scan_where / scan_combine / scan_select / scan2 (any int) -> [-1, 2^32]: every decoded
+    value lies in [0, 2^32), so this changes no comparison, and the result fits c_int64 with room for the +-1 of < and >"""
+    return min(max(int(x), -1), 1 << 32)
+
+
+def range_bounds(lo: int, hi: int) -> Optional[Tuple[int, int]]:
+    """scan_range's inclusive bounds (any ints) -> (lo, hi) within [0, 2^32), or None when no value can lie in between
+    (the rules of the C++ drop-in scan(int, int) in include/simd_scan.hpp, extended to ints beyond 32 bits)"""
+    lo, hi = int(lo), int(hi)
+    if hi < 0 or lo > hi or lo >= 1 << 32:
+        return None
+    return max(lo, 0), min(hi, 0xFFFFFFFF)
+
+
+def key32(key: int, c: int) -> int:
+    """an equality / IN-list key -> the int32 the C ABI takes.  Keys in [-2^31, 2^32) keep their meaning: the unsigned
+    32-bit pattern is compared with the decoded value, so at c = 32 a key in [-2^31, 0) matches key + 2^32, below c = 32 it
+    matches nothing.  Any other key matches nothing below c = 32 (it becomes -1, i.e. 0xffffffff >= 2^c); at c = 32 every
+    int32 pattern is a value of the column, so it raises ValueError."""
+    k = int(key)
+    if -(1 << 31) <= k < 1 << 31:
+        return k
+    if 1 << 31 <= k < 1 << 32:
+        return k - (1 << 32)
+    if c == 32:
+        raise ValueError(f"key {k} is outside [-2^31, 2^32): at c = 32 no int32 key stands for it")
+    return -1
+
+
+def keys32(keys: Sequence[int], c: int) -> np.ndarray:
+    """key32 over a key list -> contiguous int32 array"""
+    return np.ascontiguousarray(np.array([key32(k, c) for k in keys], dtype=np.int32))
+
+
 class PackedColumn:
     """A bit-packed column resident in HBM: `n` values of `c` bits, reference stream format."""
 
@@ -161,18 +200,18 @@ class ScanEngine:
             bitmap = self.alloc_bitmap(col.n)
         if hits is None:
             hits = torch.empty(1, dtype=torch.int64, device=self._dev)
-        key32 = int(np.int32(np.uint32(int(key) & 0xFFFFFFFF)))
-        check(lib().mi355_scan_eq_dev(self._ctx, col.data.data_ptr(), col.n, col.c, key32, bitmap.data_ptr(),
+        check(lib().mi355_scan_eq_dev(self._ctx, col.data.data_ptr(), col.n, col.c, key32(key, col.c), bitmap.data_ptr(),
                                       hits.data_ptr()))
         return bitmap, hits
 
     def scan_range(self, lo: int, hi: int, col: PackedColumn, bitmap: Optional[torch.Tensor] = None,
                    hits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """lo <= value <= hi (src/simd_scan.hpp:76-84)."""
+        """lo <= value <= hi (src/simd_scan.hpp:76-84); any ints, compared exactly."""
         if bitmap is None:
             bitmap = self.alloc_bitmap(col.n)
         if hits is None:
             hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        lo, hi = range_bounds(lo, hi) or (1, 0)  # lo > hi: the C side stores the empty result
         check(lib().mi355_scan_range_dev(self._ctx, col.data.data_ptr(), col.n, col.c, lo, hi, bitmap.data_ptr(),
                                          hits.data_ptr()))
         return bitmap, hits
@@ -188,7 +227,7 @@ class ScanEngine:
             bitmap = self.alloc_bitmap(col.n)
         if hits is None:
             hits = torch.empty(1, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_scan_where_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], int(a), int(b),
+        check(lib().mi355_scan_where_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
                                          and_mask.data_ptr() if and_mask is not None else None, bitmap.data_ptr(),
                                          hits.data_ptr()))
         return bitmap, hits
@@ -202,7 +241,7 @@ class ScanEngine:
             bitmap = self.alloc_bitmap(col.n)
         if hits is None:
             hits = torch.empty(1, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_scan_combine_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], int(a), int(b),
+        check(lib().mi355_scan_combine_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
                                            self._BOP[mask_op], mask.data_ptr() if mask is not None else None,
                                            None if count_only else bitmap.data_ptr(), hits.data_ptr()))
         return (None if count_only else bitmap), hits
@@ -217,8 +256,8 @@ class ScanEngine:
             bitmap = self.alloc_bitmap(col1.n)
         if hits is None:
             hits = torch.empty(1, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_scan2_dev(self._ctx, col1.data.data_ptr(), col1.c, self._CMP[op1], int(a1), int(b1), col2.data.data_ptr(),
-                                    col2.c, self._CMP[op2], int(a2), int(b2), col1.n, self._BOP[combine],
+        check(lib().mi355_scan2_dev(self._ctx, col1.data.data_ptr(), col1.c, self._CMP[op1], clamp_const(a1), clamp_const(b1),
+                                    col2.data.data_ptr(), col2.c, self._CMP[op2], clamp_const(a2), clamp_const(b2), col1.n, self._BOP[combine],
                                     None if count_only else bitmap.data_ptr(), hits.data_ptr()))
         return (None if count_only else bitmap), hits
 
@@ -228,7 +267,7 @@ class ScanEngine:
         in one launch, no bitmap in HBM; ids beyond `capacity` are dropped, count is the total."""
         rowids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self._dev)
         count = torch.empty(1, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_scan_select_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], int(a), int(b),
+        check(lib().mi355_scan_select_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
                                           self._BOP[mask_op], mask.data_ptr() if mask is not None else None, first_row,
                                           rowids.data_ptr(), capacity, count.data_ptr()))
         return rowids, count
@@ -237,7 +276,7 @@ class ScanEngine:
                 and_mask: Optional[torch.Tensor] = None, bitmap: Optional[torch.Tensor] = None,
                 hits: Optional[torch.Tensor] = None):
         """bitmap[i] = value_i in keys (NOT IN with negate=True) [& and_mask[i]]."""
-        k = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).astype(np.int32))
+        k = keys32(keys, col.c)
         if bitmap is None:
             bitmap = self.alloc_bitmap(col.n)
         if hits is None:
@@ -306,7 +345,7 @@ class ScanEngine:
         """per_predicate -> uint8[P, stride] (row k = bitmap of keys[k], stride = mi355_bitmap_stride(n): ceil(n/8) rounded up to 256);
         linear -> uint8[ceil(n/8) * P] with the byte of 8-value group g and key k at g*P + k.
         hits: int64[P] device tensor to fill (allocated when None); False skips the hit counts."""
-        k = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).astype(np.int32))
+        k = keys32(keys, col.c)
         P = int(k.shape[0])
         nb = (col.n + 7) // 8
         if hits is None:

@@ -1,6 +1,7 @@
 // dropin_tests.cpp -- the reference's own unit tests (test/simd_scan_tests.cpp, test/util_tests.cpp),
 // re-expressed against include/simd_scan.hpp (the MI355X drop-in).  Same cases, same checks; a tiny
 // REQUIRE replaces the vendored Catch.  Built and run by tests/test_dropin_cpp.py (-m gpu).
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 
@@ -60,6 +61,34 @@ static void simd_scan()
     int hits = scan(2, 3, compressed_ptr, (int)input_numbers.size(), output);
     REQUIRE(hits == 8);
     for (size_t i = 0; i < input_numbers.size(); i++) REQUIRE(get_bit(output, i) == (input_numbers[i] >= 2 && input_numbers[i] <= 3));
+}
+
+// the range scan at bounds beyond the column's domain and empty ranges: scan(int, int) compares exactly (a negative
+// lower bound is 0, a negative or smaller upper bound selects nothing) and always writes all ceil(n/8) bytes
+static void range_scan_bounds()
+{
+    const size_t n = 1000 + 5; // every 9-bit value, some twice, and a ragged last byte
+    std::vector<uint16_t> input_numbers(n);
+    for (size_t i = 0; i < n; i++) input_numbers[i] = (uint16_t)((i * 7) % (1 << BITS_NEEDED));
+    input_numbers[n - 1] = (1 << BITS_NEEDED) - 1;
+    auto compressed = compress_9bit_input(input_numbers);
+    __m128i *compressed_ptr = (__m128i *)compressed.get();
+    const int bounds[][2] = {{INT_MIN, INT_MAX}, {-5, 3}, {3, -1}, {5, 2}, {0, INT_MAX}, {INT_MIN, -1}, {INT_MAX, INT_MAX}};
+    for (const auto &lh : bounds) {
+        const long long lo = lh[0], hi = lh[1];
+        std::vector<uint8_t> output(scan_output_buffer_size(n), 0xEE);
+        int hits = scan(lh[0], lh[1], compressed_ptr, (int)n, output);
+        long long expect = 0;
+        bool ok = true;
+        for (size_t i = 0; i < n; i++) {
+            const bool in = input_numbers[i] >= lo && input_numbers[i] <= hi;
+            expect += in;
+            ok = ok && get_bit(output, i) == in;
+        }
+        for (size_t i = n; i < (n + 7) / 8 * 8; i++) ok = ok && !get_bit(output, i); // canonical tail
+        REQUIRE(ok);
+        REQUIRE(hits == expect);
+    }
 }
 
 // test/simd_scan_tests.cpp:84-106 "Shared SIMD Scan" (all nine per-predicate names)
@@ -170,6 +199,7 @@ int main(int argc, char **argv)
     try {
         compress_and_decompress();
         simd_scan();
+        range_scan_bounds();
         shared_simd_scan();
         simple_shared_simd_scan();
         util_tests();
@@ -178,6 +208,6 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 2;
     }
-    std::printf("%s (%d assertions in 6 test cases)\n", g_failed ? "FAILED" : "All tests passed", g_checks);
+    std::printf("%s (%d assertions in 7 test cases)\n", g_failed ? "FAILED" : "All tests passed", g_checks);
     return g_failed ? 1 : 0;
 }

@@ -222,6 +222,44 @@ MI355_API int mi355_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint6
 MI355_API int mi355_scan_combine_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, int op, int64_t a, int64_t b,
                                      int mask_op, const void *mask_dev, void *bitmap_dev, uint64_t *hits_dev);
 
+/* ---- shared scan over comparison predicates: P predicates `v OP a [, b]`, one pass over the column.
+ * Predicate k is exactly mi355_scan_where_dev(op_k, a_k, b_k) without a mask: unsigned comparison on the decoded value, a
+ * and b any int64 and compared as what they are (v > -5: every row; v == 2^c: none; BETWEEN 7 AND 3: none; NOT BETWEEN 7
+ * AND 3: every row; c = 32 included).  Everything else -- outputs, strides, alignment, the tail rule (exactly ceil(n/8) bytes
+ * per bitmap, bits >= n zero; linear: byte of 8-value group g and predicate k at g*P + k), hits nullable, 1 <= P <= 1024,
+ * n == 0, threading, "scan_nt_stores" -- is what mi355_shared_scan_eq_dev / _eq / _eq_linear document above.
+ *   graph capture: P <= 8 travels in the kernel arguments and is capturable; longer lists are uploaded per call through the
+ *     context's ring of pinned slots (no stream synchronisation) and are refused while the stream is capturing.
+ *   errors (MI355_E_INVALID, nothing launched, outputs untouched): op outside MI355_CMP_EQ .. MI355_CMP_NOT_BETWEEN,
+ *     reserved != 0, preds NULL, P = 0 or > 1024, unknown layout, misaligned out_dev / stride_bytes / packed_dev.
+ *   kernels: P = 1 runs the single-predicate scan.  c <= 16: one LDS byte lookup per value and 8 predicates, whatever the
+ *     predicates are, while the ceil(P/8) full tables of 2^c bytes fit in LDS next to the tiles (every P at c <= 10, P <= 256
+ *     at c = 12, P <= 8 at c = 16) -- the speed of the equality scan's byte-table kernels.  Everything else (c >= 17; longer
+ *     lists at c = 11 .. 16) runs a compare chain, VALU-bound by design: 3 VALU operations per value and predicate.  A list
+ *     whose ops are all MI355_CMP_EQ with constants that fit int32 is handed to mi355_shared_scan_eq_dev.
+ *   what it buys (profiles/r04_shared_where.txt, against P calls of mi355_scan_where_dev): tables, c = 9: 1.4 x at P = 2,
+ *     2.9 x at P = 4, 4.7 x at P = 8, 4.1 x at P = 64.  Compare chain: a pass costs the same for 1 .. 8 predicates, so it
+ *     pays from P = 3 -- c = 17 / 21: 1.8 / 2.2 x at P = 4, 3.5 / 4.3 x at P = 8, 3.6 / 4.4 x at P = 64 -- and does NOT pay
+ *     at P = 2 (c = 17: 0.88 x, two single scans are faster; c = 21: 1.07 x).  Above 8 predicates the table kernel does
+ *     one lookup per value and 8 predicates where the equality scan's dword tables do one per 32: 1.7 x the equality
+ *     scan's time at P = 64. */
+typedef struct mi355_predicate {
+    int32_t op;       /* MI355_CMP_EQ .. MI355_CMP_NOT_BETWEEN */
+    int32_t reserved; /* must be 0 */
+    int64_t a, b;     /* b is read by BETWEEN / NOT_BETWEEN only */
+} mi355_predicate;
+MI355_API int mi355_shared_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c,
+                                          const mi355_predicate *preds_host, unsigned P, int layout, void *out_dev,
+                                          uint64_t stride_bytes, uint64_t *hits_dev);
+MI355_API int mi355_shared_scan_where(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsigned c, const mi355_predicate *preds,
+                                      unsigned P, uint8_t *const *outputs, uint64_t *hits);
+MI355_API int mi355_shared_scan_where_linear(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsigned c,
+                                             const mi355_predicate *preds, unsigned P, uint8_t *output, uint64_t *hits);
+/* kernel family mi355_shared_scan_where_dev would launch for a list that is not all-MI355_CMP_EQ (nothing is launched):
+ * "scan_burst_kernel" (P = 1), "shared_where_lut_kernel" (P <= 8, c <= 16), "shared_where_lut_kernel(multi-pass)",
+ * "shared_where_chain_kernel" */
+MI355_API const char *mi355_shared_where_kernel(mi355_ctx *ctx, unsigned c, unsigned P, int layout, int with_hits);
+
 /* bitmap[i] = (v_i IN {keys[0..P-1]}) AND (and_mask ? and_mask[i] : 1), negated when `negate` != 0 (NOT IN).
  * 1 <= P <= 1024; keys as in mi355_scan_eq_dev (below c = 32, keys outside [0, 2^c) match nothing).  c <= 16: bitset
  * lookup, cost independent of P; c > 16: compare chain, O(P) per value.  and_mask_dev may be bitmap_dev itself (in place). */

@@ -51,6 +51,9 @@ SYMBOLS = [
     ("mi355_shared_scan_eq", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _vp, _vp]),
     ("mi355_shared_scan_eq_linear", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _vp, _vp]),
     ("mi355_shared_scan_eq_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _int, _vp, _u64, _vp]),
+    ("mi355_shared_scan_where", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _vp, _vp]),
+    ("mi355_shared_scan_where_linear", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _vp, _vp]),
+    ("mi355_shared_scan_where_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _int, _vp, _u64, _vp]),
     ("mi355_scan_where_dev", _int, [_vp, _vp, _u64, C.c_uint, _int, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     ("mi355_scan_combine_dev", _int, [_vp, _vp, _u64, C.c_uint, _int, C.c_int64, C.c_int64, _int, _vp, _vp, _vp]),
     ("mi355_scan2_dev", _int, [_vp, _vp, C.c_uint, _int, C.c_int64, C.c_int64, _vp, C.c_uint, _int, C.c_int64, C.c_int64, _u64, _int,
@@ -74,9 +77,15 @@ SYMBOLS = [
     ("mi355_sharded_scan_range_dev", _int, [_vp, _vp, _vp, C.c_uint, _u32, _u32, _vp, _vp, _int, _vp, _vp]),
     ("mi355_kernel_name", C.c_char_p, [C.c_char_p, C.c_uint]),
     ("mi355_shared_scan_kernel", C.c_char_p, [_vp, C.c_uint, C.c_uint, _int, _int]),
+    ("mi355_shared_where_kernel", C.c_char_p, [_vp, C.c_uint, C.c_uint, _int, _int]),
     ("mi355_ctx_last_launch", C.c_char_p, [_vp]),
     ("mi355_tile_values", _u64, [C.c_uint]),
 ]
+
+
+class Predicate(C.Structure):
+    """mi355_predicate: one comparison `v OP a [, b]` of a shared where-scan"""
+    _fields_ = [("op", C.c_int32), ("reserved", C.c_int32), ("a", C.c_int64), ("b", C.c_int64)]
 
 
 class Mi355Error(RuntimeError):

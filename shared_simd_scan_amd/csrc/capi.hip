@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dispatch.hpp"
+#include "predicates/where_dispatch.hpp"
 #include "extras/gather.hpp"
 #include "kernels.hpp"
 #include "extras/aggregate.hpp"
@@ -149,7 +150,8 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
 }
 
 constexpr int kKeySlots = 8;
-constexpr size_t kKeySlotInts = kMaxKeys + 8;
+// a slot holds the longest list of either kind: 1024 (+ 8 of padding) keys, or as many (lo, span, negate) predicate triples
+constexpr size_t kKeySlotInts = 3 * (kMaxKeys + 8);
 
 // P > 8 keys -> device memory (padded to a multiple of 8 with copies of the last key), asynchronously on the stream
 int upload_keys(mi355_ctx *ctx, const int32_t *keys_host, unsigned P, const int32_t **keys_dev)
@@ -169,6 +171,49 @@ int upload_keys(mi355_ctx *ctx, const int32_t *keys_host, unsigned P, const int3
     HIP_TRY(hipEventRecord(ctx->key_events[slot], ctx->stream));
     ctx->key_used[slot] = true;
     *keys_dev = d;
+    return MI355_OK;
+}
+
+// P > 8 normalised predicates -> device memory as (lo, span, negate) triples, padded to a multiple of 8 predicates with
+// copies of the last: the key ring above, the same rules
+int upload_preds(mi355_ctx *ctx, const uint32_t *triples_host, unsigned P, const uint32_t **preds_dev)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail(MI355_E_INVALID, "predicate lists longer than 8 are uploaded per call and cannot be captured into a graph");
+    const int slot = ctx->key_next;
+    ctx->key_next = (slot + 1) % kKeySlots;
+    if (ctx->key_used[slot]) HIP_TRY(hipEventSynchronize(ctx->key_events[slot])); // the copy out of this slot is done
+    uint32_t *h = (uint32_t *)(ctx->keys_pinned + (size_t)slot * kKeySlotInts);
+    uint32_t *d = (uint32_t *)(ctx->keys_scratch + (size_t)slot * kKeySlotInts);
+    const unsigned npad = (P + 7) / 8 * 8;
+    memcpy(h, triples_host, (size_t)P * 3 * sizeof(uint32_t));
+    for (unsigned k = P; k < npad; k++) memcpy(h + 3 * k, triples_host + 3 * (P - 1), 3 * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(d, h, (size_t)npad * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->key_events[slot], ctx->stream));
+    ctx->key_used[slot] = true;
+    *preds_dev = d;
+    return MI355_OK;
+}
+
+typedef hipError_t (*where_group_fn)(const WhereReq &);
+const where_group_fn kWhereGroups[kNumGroups] = {launch_where_group_0, launch_where_group_1, launch_where_group_2, launch_where_group_3,
+                                                 launch_where_group_4, launch_where_group_5, launch_where_group_6, launch_where_group_7};
+
+// the kernels of predicates/ take no switch word (their launch records read flags=0x0) and are not tuned per device
+int launch_where(mi355_ctx *ctx, WhereReq &r)
+{
+    if (int rc = bind(ctx)) return rc;
+    r.l.stream = ctx->stream;
+    r.l.device = ctx->device;
+    r.l.num_cus = grid_cus(ctx);
+    r.l.record = &ctx->last_launch;
+    r.l.max_blocks_per_cu = ctx->max_blocks_per_cu;
+    r.l.scan_nt_stores = ctx->scan_nt_stores;
+    r.w.s.flags = 0;
+    r.w.s.scratch = ctx->kernel_scratch;
+    hipError_t e = kWhereGroups[(r.l.c - 1) / 4](r);
+    if (e != hipSuccess) return fail(MI355_E_HIP, "kernel launch (shared where-scan, c=%u): %s", r.l.c, hipGetErrorString(e));
     return MI355_OK;
 }
 
@@ -220,8 +265,8 @@ int mi355_ctx_create(int device, void *hip_stream, mi355_ctx **out)
     hipError_t e = hipHostMalloc((void **)&c->hits_scratch, kMaxKeys * sizeof(unsigned long long), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc((void **)&c->kernel_scratch, kScratchWords * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(c->kernel_scratch, 0, kScratchWords * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->keys_scratch, 8 * (kMaxKeys + 8) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->keys_pinned, 8 * (kMaxKeys + 8) * sizeof(int32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->keys_scratch, kKeySlots * kKeySlotInts * sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->keys_pinned, kKeySlots * kKeySlotInts * sizeof(int32_t), hipHostMallocDefault);
     for (int i = 0; i < 8 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&c->key_events[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->order_event, hipEventDisableTiming);
     if (e != hipSuccess) {
@@ -795,6 +840,78 @@ int mi355_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, uns
     return mi355_scan_combine_dev(ctx, packed_dev, n, c, op, a, b, MI355_BITMAP_AND, and_mask_dev, bitmap_dev, hits_dev);
 }
 
+// P comparison predicates in one pass (kernels: predicates/where.hpp).  Each predicate goes through fill_predicate, the
+// normalisation of the single-predicate scan: (lo, span, negation word).
+int mi355_shared_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, const mi355_predicate *preds_host,
+                                unsigned P, int layout, void *out_dev, uint64_t stride_bytes, uint64_t *hits_dev)
+{
+    int rc = resolve(ctx);
+    if (rc) return rc;
+    CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
+    if ((rc = check_width(c))) return rc;
+    if (P < 1 || P > (unsigned)kMaxKeys) return fail(MI355_E_INVALID, "P=%u outside 1..%u", P, kMaxKeys);
+    if (!preds_host) return fail(MI355_E_INVALID, "preds is null");
+    if (layout != MI355_LAYOUT_PER_PREDICATE && layout != MI355_LAYOUT_LINEAR)
+        return fail(MI355_E_INVALID, "unknown layout %d", layout);
+    bool all_eq = true; // ... with constants the equality call's int32 keys can carry
+    const int64_t vmax = c == 32 ? 0xffffffffll : ((1ll << c) - 1);
+    for (unsigned k = 0; k < P; k++) {
+        const mi355_predicate &p = preds_host[k];
+        if (p.op < MI355_CMP_EQ || p.op > MI355_CMP_NOT_BETWEEN) return fail(MI355_E_INVALID, "preds[%u]: unknown comparison %d", k, p.op);
+        if (p.reserved != 0) return fail(MI355_E_INVALID, "preds[%u]: reserved must be 0", k);
+        if (p.op != MI355_CMP_EQ || ((p.a < 0 || p.a > vmax) ? c == 32 : p.a > 0x7fffffffll)) all_eq = false;
+    }
+    if (n == 0) {
+        if (hits_dev) HIP_TRY(hipMemsetAsync(hits_dev, 0, P * sizeof(uint64_t), ctx->stream));
+        return MI355_OK;
+    }
+    if (!packed_dev || !out_dev) return fail(MI355_E_INVALID, "null device pointer");
+    if (((uintptr_t)packed_dev & 15) != 0) return fail(MI355_E_INVALID, "packed_dev must be 16-byte aligned");
+    if (layout == MI355_LAYOUT_PER_PREDICATE) {
+        if (((uintptr_t)out_dev & 15) != 0 || (stride_bytes & 15) != 0)
+            return fail(MI355_E_INVALID, "out_dev and stride_bytes must be multiples of 16");
+        if (stride_bytes < bitmap_bytes(n)) return fail(MI355_E_INVALID, "stride_bytes smaller than ceil(n/8)");
+    } else if (((uintptr_t)out_dev & 15) != 0) {
+        return fail(MI355_E_INVALID, "out_dev must be 16-byte aligned");
+    }
+    // one predicate: both layouts are its plain bitmap -- the single-predicate scan kernel
+    if (P == 1)
+        return mi355_scan_combine_dev(ctx, packed_dev, n, c, preds_host[0].op, preds_host[0].a, preds_host[0].b, MI355_BITMAP_AND, nullptr,
+                                      out_dev, hits_dev);
+    if (all_eq) { // literal equalities: the equality machinery (digit tables at every width, 32 keys per lookup)
+        int32_t keys[kMaxKeys];
+        for (unsigned k = 0; k < P; k++) keys[k] = (preds_host[k].a < 0 || preds_host[k].a > vmax) ? -1 : (int32_t)preds_host[k].a;
+        return mi355_shared_scan_eq_dev(ctx, packed_dev, n, c, keys, P, layout, out_dev, stride_bytes, hits_dev);
+    }
+    WhereReq r{};
+    r.l.op = kOpSharedScan;
+    r.l.c = c;
+    r.w.s.packed = (const uint8_t *)packed_dev;
+    r.w.s.n = n;
+    r.w.s.out = (uint8_t *)out_dev;
+    r.w.s.out_stride = stride_bytes;
+    r.w.s.hits = (unsigned long long *)hits_dev;
+    r.w.s.nkeys = P;
+    r.w.s.layout = (uint32_t)layout;
+    auto normalise = [&](unsigned k, uint32_t *lo, uint32_t *span, uint32_t *neg) {
+        ScanArgs one{};
+        fill_predicate(one, c, preds_host[k].op, preds_host[k].a, preds_host[k].b);
+        *lo = one.key[0];
+        *span = one.key[1];
+        *neg = one.invert;
+    };
+    if (P <= (unsigned)kMaxKeysPerPass) {
+        for (unsigned q = 0; q < (unsigned)kMaxKeysPerPass; q++) normalise(q < P ? q : P - 1, &r.w.lo[q], &r.w.span[q], &r.w.neg[q]);
+    } else {
+        uint32_t triples[3 * kMaxKeys];
+        for (unsigned k = 0; k < P; k++) normalise(k, &triples[3 * k], &triples[3 * k + 1], &triples[3 * k + 2]);
+        if ((rc = bind(ctx))) return rc;
+        if ((rc = upload_preds(ctx, triples, P, &r.w.preds_dev))) return rc;
+    }
+    return launch_where(ctx, r);
+}
+
 int mi355_scan_in_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, const int32_t *keys_host, unsigned P,
                       int negate, const void *and_mask_dev, void *bitmap_dev, uint64_t *hits_dev)
 {
@@ -1176,8 +1293,10 @@ int mi355_scan_range(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsign
     return scan_host(ctx, kOpScanRange, packed_host, n, c, lo, hi, bitmap_host, hits);
 }
 
+// keys (equality) or preds (comparison predicates): exactly one of them is non-null
 static int shared_host(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsigned c, const int32_t *keys, unsigned P,
-                       int layout, uint8_t *const *outputs, uint8_t *linear_out, uint64_t *hits)
+                       int layout, uint8_t *const *outputs, uint8_t *linear_out, uint64_t *hits, const mi355_predicate *preds = nullptr,
+                       bool where = false)
 {
     int rc = resolve(ctx);
     if (rc) return rc;
@@ -1185,7 +1304,7 @@ static int shared_host(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsi
     CallScope cs(ctx);
     if ((rc = check_width(c))) return rc;
     if (P < 1 || P > (unsigned)kMaxKeys) return fail(MI355_E_INVALID, "P=%u outside 1..%u", P, kMaxKeys);
-    if (!keys) return fail(MI355_E_INVALID, "keys is null");
+    if (where ? !preds : !keys) return fail(MI355_E_INVALID, where ? "preds is null" : "keys is null");
     if (hits) memset(hits, 0, P * sizeof(uint64_t));
     if (n == 0) return MI355_OK;
     if (!packed_host || (layout == MI355_LAYOUT_PER_PREDICATE ? !outputs : !linear_out))
@@ -1197,7 +1316,9 @@ static int shared_host(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsi
     if ((rc = upload_packed(ctx, packed_host, n, c, &dp))) return rc;
     if ((rc = pool_get(ctx, mi355_ctx::kPoolOut, (layout == MI355_LAYOUT_PER_PREDICATE ? stride : nb) * P + 16, &dout))) return rc;
     // the reference's shared scans return no counts: only count when the caller asked
-    if ((rc = mi355_shared_scan_eq_dev(ctx, dp, n, c, keys, P, layout, dout, stride, hits ? (uint64_t *)ctx->hits_scratch : nullptr)))
+    uint64_t *const hits_dev = hits ? (uint64_t *)ctx->hits_scratch : nullptr;
+    if ((rc = where ? mi355_shared_scan_where_dev(ctx, dp, n, c, preds, P, layout, dout, stride, hits_dev)
+                    : mi355_shared_scan_eq_dev(ctx, dp, n, c, keys, P, layout, dout, stride, hits_dev)))
         return rc;
     if (layout == MI355_LAYOUT_PER_PREDICATE) {
         for (unsigned k = 0; k < P; k++) {
@@ -1221,6 +1342,17 @@ int mi355_shared_scan_eq_linear(mi355_ctx *ctx, const void *packed_host, uint64_
                                 unsigned P, uint8_t *output, uint64_t *hits)
 {
     return shared_host(ctx, packed_host, n, c, keys, P, MI355_LAYOUT_LINEAR, nullptr, output, hits);
+}
+
+int mi355_shared_scan_where(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsigned c, const mi355_predicate *preds, unsigned P,
+                            uint8_t *const *outputs, uint64_t *hits)
+{
+    return shared_host(ctx, packed_host, n, c, nullptr, P, MI355_LAYOUT_PER_PREDICATE, outputs, nullptr, hits, preds, true);
+}
+int mi355_shared_scan_where_linear(mi355_ctx *ctx, const void *packed_host, uint64_t n, unsigned c, const mi355_predicate *preds,
+                                   unsigned P, uint8_t *output, uint64_t *hits)
+{
+    return shared_host(ctx, packed_host, n, c, nullptr, P, MI355_LAYOUT_LINEAR, nullptr, output, hits, preds, true);
 }
 
 /* ---- introspection ---- */
@@ -1272,6 +1404,26 @@ const char *mi355_shared_scan_kernel(mi355_ctx *ctx, unsigned c, unsigned P, int
     static const char *const names[] = {"shared_lut_kernel", "shared_lut_kernel(multi-pass)", "shared_wide_kernel", "shared_general_kernel",
                                         "shared_linear_kernel", "shared_pair_kernel"};
     return choice >= 0 && choice < 6 ? names[choice] : nullptr;
+}
+
+const char *mi355_shared_where_kernel(mi355_ctx *ctx, unsigned c, unsigned P, int layout, int with_hits)
+{
+    if (resolve(ctx) != MI355_OK) return nullptr;
+    if (c < 1 || c > 32 || P < 1 || P > (unsigned)kMaxKeys) return nullptr;
+    if (P == 1) return "scan_burst_kernel";
+    CtxLock lk(ctx->mu);
+    WhereReq r{};
+    int choice = -1;
+    unsigned long long dummy = 0;
+    r.l.c = c;
+    r.l.choice_out = &choice;
+    r.w.s.n = 1;
+    r.w.s.nkeys = P;
+    r.w.s.layout = (uint32_t)layout;
+    r.w.s.hits = with_hits ? &dummy : nullptr;
+    if (launch_where(ctx, r) != MI355_OK) return nullptr;
+    static const char *const names[] = {"shared_where_lut_kernel", "shared_where_lut_kernel(multi-pass)", "shared_where_chain_kernel"};
+    return choice >= 0 && choice < 3 ? names[choice] : nullptr;
 }
 
 uint64_t mi355_tile_values(unsigned c)

@@ -33,10 +33,11 @@ struct mi355_ctx {
     std::recursive_mutex mu;
     unsigned long long *hits_scratch = nullptr; // host-pointer API: where the kernels deliver hit counts
     unsigned long long *kernel_scratch = nullptr; // kScratchWords words, all zero between launches (kernels.hpp hits_finalize)
-    // key lists longer than 8 travel through device memory: a ring of kKeySlots pinned host slots and device slots of
-    // 1024 + 8 keys each, so uploading a list never waits for the stream (only for the copy that used the slot
+    // key lists (and predicate lists of the shared where-scans) longer than 8 travel through device memory: a ring of
+    // kKeySlots pinned host slots and device slots of 3 x (1024 + 8) dwords each -- 1024 + 8 keys, or as many (lo, span,
+    // negate) predicate triples -- so uploading a list never waits for the stream (only for the copy that used the slot
     // kKeySlots calls ago)
-    int32_t *keys_scratch = nullptr;            // device: kKeySlots x (1024 + 8) keys
+    int32_t *keys_scratch = nullptr;            // device: kKeySlots x 3 x (1024 + 8) dwords
     int32_t *keys_pinned = nullptr;             // host (pinned): the same
     hipEvent_t key_events[8] = {};
     bool key_used[8] = {};

@@ -83,6 +83,33 @@ def keys32(keys: Sequence[int], c: int) -> np.ndarray:
     return np.ascontiguousarray(np.array([key32(k, c) for k in keys], dtype=np.int32))
 
 
+CMP = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "between": 6, "not_between": 7}
+
+
+def predicates(preds: Sequence[Tuple]) -> "C.Array":
+    """(op, a) / (op, a, b) tuples, op spelled as scan_where spells it and a, b any ints -> the mi355_predicate array of
+    mi355_shared_scan_where_dev.  Constants go through clamp_const; b is 0 where the op does not read it."""
+    arr = (_capi.Predicate * max(len(preds), 1))()
+    for i, p in enumerate(preds):
+        if len(p) not in (2, 3):
+            raise ValueError(f"predicate {i}: expected (op, a) or (op, a, b), got {p!r}")
+        op = CMP[p[0]]
+        arr[i].op = op
+        arr[i].reserved = 0
+        arr[i].a = clamp_const(p[1])
+        arr[i].b = clamp_const(p[2]) if len(p) == 3 and op >= 6 else 0
+    return arr
+
+
+def shared_where_kernel(c: int, P: int, layout: str = "per_predicate", with_hits: bool = True) -> str:
+    """kernel family a shared where-scan of P predicates at width c launches (mi355_shared_where_kernel; needs a device)"""
+    code = {"per_predicate": _capi.LAYOUT_PER_PREDICATE, "linear": _capi.LAYOUT_LINEAR}[layout]
+    s = lib().mi355_shared_where_kernel(None, c, P, code, 1 if with_hits else 0)
+    if s is None:
+        raise ValueError((c, P, layout))
+    return s.decode()
+
+
 class PackedColumn:
     """A bit-packed column resident in HBM: `n` values of `c` bits, reference stream format."""
 
@@ -217,7 +244,7 @@ class ScanEngine:
         return bitmap, hits
 
     # ---- beyond the reference: general comparisons, conjunctions, bitmap consumers -----
-    _CMP = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "between": 6, "not_between": 7}
+    _CMP = CMP
     _BOP = {"and": 0, "or": 1, "xor": 2, "andnot": 3}
 
     def scan_where(self, op: str, a: int, col: PackedColumn, b: int = 0, and_mask: Optional[torch.Tensor] = None,
@@ -365,4 +392,31 @@ class ScanEngine:
             raise ValueError(layout)
         check(lib().mi355_shared_scan_eq_dev(self._ctx, col.data.data_ptr(), col.n, col.c, k.ctypes.data, P, code,
                                              out.data_ptr(), stride, hits_ptr))
+        return out, (None if hits is False else hits)
+
+    def shared_scan_where(self, preds: Sequence[Tuple], col: PackedColumn, layout: str = "per_predicate",
+                          out: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):
+        """shared_scan over comparison predicates: preds = (op, a) / (op, a, b) tuples, op in == != < <= > >= between
+        not_between, constants any ints; predicate k is scan_where(op_k, a_k, col, b_k).  Outputs, `hits` and the return
+        value as shared_scan."""
+        arr = predicates(preds)
+        P = len(preds)
+        nb = (col.n + 7) // 8
+        if hits is None:
+            hits = torch.empty(P, dtype=torch.int64, device=self._dev)
+        hits_ptr = 0 if hits is False else hits.data_ptr()
+        if layout == "per_predicate":
+            stride = int(lib().mi355_bitmap_stride(col.n))
+            if out is None:
+                out = torch.empty((P, stride), dtype=torch.uint8, device=self._dev)
+            code = _capi.LAYOUT_PER_PREDICATE
+        elif layout == "linear":
+            stride = 0
+            if out is None:
+                out = self._empty(nb * P)
+            code = _capi.LAYOUT_LINEAR
+        else:
+            raise ValueError(layout)
+        check(lib().mi355_shared_scan_where_dev(self._ctx, col.data.data_ptr(), col.n, col.c, C.cast(arr, C.c_void_p), P, code,
+                                                out.data_ptr(), stride, hits_ptr))
         return out, (None if hits is False else hits)

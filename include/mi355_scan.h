@@ -96,7 +96,11 @@ MI355_API int mi355_ctx_set_stream(mi355_ctx *ctx, void *hip_stream);
  * the HBM->LDS loads, 0 default / 2 non-temporal; bit 4: non-temporal output stores in decompress; default 18),
  * "scan_nt_stores" (result stores of the scans: -1 chosen by output size (default: write-through while the bitmap fits
  * the Infinity Cache, non-temporal beyond), 0 plain, 1 non-temporal, 2 write-through), "select_kernel" (mi355_scan_select_dev:
- * 0 / 2 = decoder / expander roles (default), 1 = the older single-role kernel, kept for A/B runs), "kernel_flags" (A/B switches of the kernels; results never depend on them except the two timing
+ * 0 / 2 = decoder / expander roles (default), 1 = the older single-role kernel, kept for A/B runs), "llc_resident_mib" (equality / range scans: MiB of the 256 MiB Infinity Cache
+ * for the part of the column that is read with the default cache policy and so stays there for the next scan; -1 (default) a measured budget, applied
+ * ONLY when the context's previous launch was a scan of the same column (pointer, n, c) into the same bitmap with the same mask, i.e. to back-to-back
+ * identical buffers -- predicates written to different bitmaps, or a chain whose mask changes, never qualify; a scan captured into a graph keeps the
+ * decision made at capture time; 0 off; 1 .. 1024 an explicit budget for every call), "kernel_flags" (A/B switches of the kernels; results never depend on them except the two timing
  * ablations of the selection documented in DESIGN.md), "grid_cus" (0 = the device's CU count (default); 1 .. CU count: every
  * persistent grid is sized as if the device had that many CUs -- with "max_blocks_per_cu" = 1 and "grid_cus" = 1 a launch runs
  * 4 waves, each of which walks thousands of tiles of a large column: the long-loop paths tests need; other values are rejected
@@ -381,6 +385,9 @@ MI355_API const char *mi355_shared_scan_kernel(mi355_ctx *ctx, unsigned c, unsig
  * options, stream, memory helpers and introspection calls leave it alone.  Host-side text only: recording adds no device work.
  * The string stays valid until the calling thread calls this function again; NULL when ctx cannot be resolved. */
 MI355_API const char *mi355_ctx_last_launch(mi355_ctx *ctx);
+/* "llc_resident_mib": the divisor D the most recent launch ran with if it was an equality / range scan (0 nothing resident, 1 the whole
+ * column, else every D-th 64 KiB granule), -1 otherwise.  Introspection for tests, like the launch record. */
+MI355_API int mi355_ctx_last_llc_divisor(mi355_ctx *ctx);
 /* rows per wave tile of the scan kernels at width c (shard boundaries should be multiples of it) */
 MI355_API uint64_t mi355_tile_values(unsigned c);
 

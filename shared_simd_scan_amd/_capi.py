@@ -79,6 +79,7 @@ SYMBOLS = [
     ("mi355_shared_scan_kernel", C.c_char_p, [_vp, C.c_uint, C.c_uint, _int, _int]),
     ("mi355_shared_where_kernel", C.c_char_p, [_vp, C.c_uint, C.c_uint, _int, _int]),
     ("mi355_ctx_last_launch", C.c_char_p, [_vp]),
+    ("mi355_ctx_last_llc_divisor", C.c_int, [_vp]),
     ("mi355_tile_values", _u64, [C.c_uint]),
 ]
 

@@ -128,6 +128,16 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
     r.scan_nt_stores = ctx->scan_nt_stores;
     r.shared_vpl = ctx->shared_vpl;
     r.scan_burst = ctx->scan_burst;
+    r.llc_resident_mib = ctx->llc_resident_mib;
+    ctx->llc_last_d = -1;
+    r.llc_d_out = &ctx->llc_last_d;
+    if (r.op == kOpScanEq || r.op == kOpScanRange) {
+        r.llc_repeat = ctx->llc_prev[0] == r.scan.packed && ctx->llc_prev[1] == r.scan.out && ctx->llc_prev[2] == r.scan.and_mask &&
+                       ctx->llc_prev_n == r.scan.n && ctx->llc_prev_c == r.c;
+        ctx->llc_prev[0] = r.scan.packed, ctx->llc_prev[1] = r.scan.out, ctx->llc_prev[2] = r.scan.and_mask;
+        ctx->llc_prev_n = r.scan.n, ctx->llc_prev_c = r.c;
+    } else
+        ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
     // the A/B switches of the shared scans (bits 0-8) never reach the selection kernels, whose switches live in bits 9-12 of
     // the option and arrive as their bits 1-4: two TIMING ablations (2 no expansion, 4 no look-back: wrong ids by construction)
     // and two A/B switches of select_kernel's chunk hand-out (8 chunks dealt out by block index as in round 2, 16 no barrier
@@ -259,6 +269,7 @@ int mi355_ctx_create(int device, void *hip_stream, mi355_ctx **out)
     if (const char *s = getenv("MI355_MAX_BLOCKS_PER_CU")) c->max_blocks_per_cu = atoi(s);
     if (const char *s = getenv("MI355_DMA_AUX")) c->dma_aux = atoi(s);
     if (const char *s = getenv("MI355_SCAN_BURST")) c->scan_burst = atoi(s);
+    if (const char *s = getenv("MI355_LLC_RESIDENT_MIB")) c->llc_resident_mib = atoi(s);
     if (const char *s = getenv("MI355_SHARED_VPL")) c->shared_vpl = atoi(s);
     if (const char *s = getenv("MI355_KERNEL_FLAGS")) c->kernel_flags = (unsigned)atoi(s);
     // host-pointer flavours: the kernels write the hit counts here, straight into pinned (device-visible) host memory
@@ -365,7 +376,10 @@ int mi355_ctx_set_option(mi355_ctx *ctx, const char *name, int value)
         ctx->select_kernel = value;
     else if (!strcmp(name, "scan_burst"))
         ctx->scan_burst = value;
-    else if (!strcmp(name, "kernel_flags"))
+    else if (!strcmp(name, "llc_resident_mib")) {
+        if (value < -1 || value > 1024) return fail(MI355_E_INVALID, "llc_resident_mib=%d outside -1..1024", value);
+        ctx->llc_resident_mib = value;
+    } else if (!strcmp(name, "kernel_flags"))
         ctx->kernel_flags = (unsigned)value;
     else if (!strcmp(name, "grid_cus")) {
         if (value < 0 || value > ctx->num_cus) return fail(MI355_E_INVALID, "grid_cus=%d outside 0..%d", value, ctx->num_cus);
@@ -1356,6 +1370,13 @@ int mi355_shared_scan_where_linear(mi355_ctx *ctx, const void *packed_host, uint
 }
 
 /* ---- introspection ---- */
+int mi355_ctx_last_llc_divisor(mi355_ctx *ctx)
+{
+    if (resolve(ctx) != MI355_OK) return -1;
+    CtxLock lk(ctx->mu);
+    return ctx->llc_last_d;
+}
+
 const char *mi355_ctx_last_launch(mi355_ctx *ctx)
 {
     static thread_local std::string copy;

@@ -25,6 +25,13 @@ struct mi355_ctx {
     // mi355_tune_dev: blocks per CU measured on THIS device for the large streaming launches; key = tune_key() in capi.hip
     std::map<uint32_t, int> tuned_bpc;
     int scan_burst = 0;  // 0: tiles per store burst by width; 1: one tile per burst
+    int llc_resident_mib = -1; // eq / range scan: MiB of Infinity Cache for the part of the column read with the default policy; -1 auto, 0 off
+    // the buffers of the previous kernel launch if it was an eq / range scan (else null): auto keeps part of a column resident
+    // only when a scan repeats them, i.e. when what the cache holds is this column and this bitmap
+    const void *llc_prev[3] = {nullptr, nullptr, nullptr}; // column, bitmap, mask
+    int llc_last_d = -1;   // mi355_ctx_last_llc_divisor: ScanArgs::llc_d of the most recent launch, -1 if that was not an eq / range scan
+    uint64_t llc_prev_n = 0;
+    unsigned llc_prev_c = 0;
     int dma_aux = 18; // bits 0-3: policy of the HBM->LDS loads (2 = non-temporal: the column is streamed once);
                       // bit 4: non-temporal stores in decompress
     // Every entry point that touches the state below holds `mu` while it does (the host-pointer flavours from their

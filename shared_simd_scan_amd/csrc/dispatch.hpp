@@ -82,6 +82,9 @@ struct LaunchReq {
     int dma_aux;           // cache policy of the HBM->LDS loads: 0 default, 2 nt
     int scan_nt_stores;    // bitmap stores of the eq / range scan: -1 by size, 0 plain, 1 non-temporal
     int scan_burst;        // eq / range scan: 0 = tiles per store burst chosen by width (burst_k), 1 = one tile per burst
+    int llc_resident_mib;  // eq / range scan: Infinity Cache budget of the column's resident part, -1 auto, 0 off (width_group.hip llc_divisor)
+    int llc_repeat;        // eq / range scan: the context's previous call was a scan of the same column into the same bitmap (auto acts on repeats only)
+    int *llc_d_out;        // eq / range scan: non-null = where the launcher reports the divisor it chose (mi355_ctx_last_llc_divisor)
     int select_single;     // kOpSelect: 1 = the older single-role kernel (option "select_kernel" = 1, A/B), 0 = decoder / expander roles
     int shared_vpl;        // shared scans of <= 8 keys: values per lane and tile, 0 = the engine's choice, 64, 128 (c <= 12)
     std::string *record;   // the context's launch record (mi355_ctx_last_launch), null = not recorded

@@ -15,13 +15,26 @@ namespace mi355 {
 template <int C, int VPL> struct TileCtx {
     using G = ScanGeom<C, VPL>;
     uint64_t n, ntiles, nfull, data_bytes;
-    __device__ __forceinline__ TileCtx(uint64_t n_) : n(n_)
+    uint32_t llc_inv, llc_lim; // ScanArgs::llc_inv / llc_lim; 0, 0 (every kernel but scan_burst_kernel): the branch in issue() folds away
+    __device__ __forceinline__ TileCtx(uint64_t n_, uint32_t llc_inv_ = 0, uint32_t llc_lim_ = 0) : n(n_), llc_inv(llc_inv_), llc_lim(llc_lim_)
     {
         ntiles = (n + G::TILE_VALUES - 1) / G::TILE_VALUES;
         nfull = n / G::TILE_VALUES;
         data_bytes = (n * C + 7) / 8;
     }
     template <int AUX> __device__ __forceinline__ void issue(const uint8_t *packed, uint64_t t, uint8_t *lds_wave, int lane) const
+    {
+        if constexpr (AUX != 0) {
+            // a tile that starts in a resident granule (ScanArgs::llc_d) is loaded with the default policy, so that the next launch
+            // finds it in the Infinity Cache: a function of the byte offset only (t is wave-uniform: one scalar branch)
+            if (llc_inv != 0 && (uint32_t)((t * G::TILE_BYTES) >> kLlcGranuleShift) * llc_inv <= llc_lim) {
+                issue_as<0>(packed, t, lds_wave, lane);
+                return;
+            }
+        }
+        issue_as<AUX>(packed, t, lds_wave, lane);
+    }
+    template <int AUX> __device__ __forceinline__ void issue_as(const uint8_t *packed, uint64_t t, uint8_t *lds_wave, int lane) const
     {
         const uint8_t *src = packed + t * G::TILE_BYTES;
         if (t < nfull)
@@ -95,7 +108,7 @@ __global__ __launch_bounds__(kBlockThreads, (burst_occ<C, VPL, K>())) void scan_
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t *lds_wave = lds[wave];
     uint8_t *mlds_wave = mlds[wave];
-    const TileCtx<C, VPL> tc(a.n);
+    const TileCtx<C, VPL> tc(a.n, a.llc_inv, a.llc_lim);
     const uint64_t nchunks = (tc.ntiles + K - 1) / K;
     const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
     uint64_t chunk = (uint64_t)blockIdx.x * kWavesPerBlock + wave;

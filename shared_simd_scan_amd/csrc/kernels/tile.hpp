@@ -91,7 +91,24 @@ struct ScanArgs {
     uint64_t *rowids;          // select_kernel: ascending row ids out
     uint64_t capacity;         // select_kernel: at most this many ids are written
     uint64_t first_row;        // select_kernel: global row index of row 0
+    uint32_t llc_d;            // scan_burst_kernel: part of the column kept in the Infinity Cache between launches (option "llc_resident_mib"):
+                               // 64 KiB granule g of `packed` is RESIDENT iff g mod llc_d == 0 (0 none, 1 every granule, else odd).  A tile that
+                               // starts in a resident granule is loaded with the default cache policy, any other with the kernel's own (nt)
+    uint32_t llc_inv, llc_lim; // the same test without a division (llc_d odd): g * llc_inv mod 2^32 <= llc_lim; llc_inv = 0: nothing resident
 };
+constexpr int kLlcGranuleShift = 16;
+// host side: the two words of the divisibility test for an odd d (d = 1: every granule); d = 0 leaves both zero
+inline void llc_set(ScanArgs &a, uint32_t d)
+{
+    a.llc_d = d;
+    a.llc_inv = 0;
+    a.llc_lim = 0;
+    if (d == 0) return;
+    uint32_t inv = d; // Newton: the inverse of an odd d modulo 2^32 (d * d = 1 mod 8: three bits to start with)
+    for (int i = 0; i < 5; i++) inv *= 2u - d * inv;
+    a.llc_inv = inv;
+    a.llc_lim = 0xffffffffu / d;
+}
 // `out` may be null in scan_burst_kernel / scan2_kernel: count-only scan (hits without a bitmap).
 
 // ---- DMA: HBM -> LDS ---------------------------------------------------------------------------

@@ -78,6 +78,36 @@ template <int C, int VPL> bool lut8_fits(uint32_t P)
 // (0.184 against 0.177), is neutral at c <= 4, and -2 % at 64 values per lane (c >= 17).
 constexpr int burst_k(int c) { return (c == 5 || c == 6 || (c >= 9 && c <= 16)) ? 4 : 1; }
 
+// Part of a column that the eq / range scan keeps in the 256 MiB Infinity Cache between launches (option "llc_resident_mib";
+// ScanArgs::llc_d): 0 none, 1 all of it, else every d-th 64 KiB granule, d odd, so that with grids of a power of two times the
+// CU count every wave meets the same share in every round.  resident bytes = min(column, budget - the bitmaps the call writes
+// and reads, which live in the cache too).  Measured with launches back to back on one column (tools/llc_slice.hip,
+// profiles/r05_llc_slice.txt, medians), 1e9 x 9 bit, 119 MiB of bitmap, write-through stores, against 0.1985 ms with nothing
+// resident: 63 / 98 MiB (d = 17 / 11) 0.1908 / 0.1900 (-3.9 / -4.3 %), 119 MiB (d = 9) 0.1986, 153 MiB 0.2031 (+2 %): the gain
+// ends between 217 and 238 MiB of column part plus bitmap.  The product in one process (profiles/r05_llc_ab.txt, tools/ab_opts.py):
+// budgets 190 / 205 / 220 / 240 MiB (d = 17 / 13 / 11 / 9) 0.1947 / 0.1933 / 0.1950 / 0.2048 against 0.2026 ms, hence
+// kLlcAutoMiB = 205: the best measured, and a step further from the cliff than 220.  5e8 rows: 0.0983 -> 0.0893 (d = 5, what 205
+// gives there); 2.5e8: 0.0492 -> 0.0460 (d = 3).  A column that fits whole gains nothing (1.25e8 rows: 0.0227 against 0.0228 ms;
+// the product at 1e8 rows +3 %): auto leaves d = 1 to an explicit budget.
+// When the column is NOT what the cache holds -- two 1e9-row columns scanned in turn, each into its own bitmap -- any resident
+// part costs (16 / 33 / 98 MiB: +8 / +14 / +17 %: the default-policy loads push the other scan's dirty bitmap lines out to HBM),
+// so auto acts only on a repeat: the context's previous launch was a scan of the same column, bitmap and mask
+// (LaunchReq::llc_repeat).  An explicit budget (> 0) applies to every call.
+constexpr int kLlcAutoMiB = 205;
+inline uint32_t llc_divisor(const LaunchReq &r, uint64_t column_bytes, uint64_t bitmap_bytes)
+{
+    if (r.llc_resident_mib == 0 || (r.dma_aux & 15) == 0) return 0; // off; dma_aux = 0: every load has the default policy anyway
+    if (bitmap_bytes > (768ull << 20)) return 0;                    // the bitmap alone is far beyond the cache (see launch_scan)
+    const bool automatic = r.llc_resident_mib < 0;
+    if (automatic && !r.llc_repeat) return 0;
+    const uint64_t budget = (uint64_t)(automatic ? kLlcAutoMiB : r.llc_resident_mib) << 20;
+    if (budget <= bitmap_bytes) return 0;
+    const uint64_t resident = budget - bitmap_bytes;
+    if (resident >= column_bytes) return automatic ? 0 : 1;
+    const uint64_t d = ((column_bytes + resident - 1) / resident) | 1u; // >= 3, odd
+    return d > 0x7fffffu ? 0 : (uint32_t)d;
+}
+
 template <int C, int MODE> void launch_scan(const LaunchReq &r)
 {
     constexpr int VPL = scan_vpl(C, MODE);
@@ -90,18 +120,21 @@ template <int C, int MODE> void launch_scan(const LaunchReq &r)
     // Bitmaps far beyond the 256 MiB Infinity Cache prefer non-temporal stores: 4e9 rows sc1 0.82 ms / nt 0.85,
     // 8e9 rows (1 GB of bitmap) 1.74 / 1.72.
     const int policy = r.scan_nt_stores < 0 ? (r.scan.n / 8 > (768ull << 20) ? 1 : 2) : r.scan_nt_stores; // 0 plain, 1 nt, 2 sc1
+    ScanArgs a = r.scan;
+    llc_set(a, llc_divisor(r, (r.scan.n * C + 7) / 8, (r.scan.out ? (r.scan.n + 7) / 8 : 0) + (r.scan.and_mask ? (r.scan.n + 7) / 8 : 0)));
+    if (r.llc_d_out) *r.llc_d_out = (int)a.llc_d;
     auto go = [&](auto kc) {
         constexpr int K = decltype(kc)::value;
         static const int bpcK = blocks_per_cu(scan_burst_kernel<C, MODE, 34, VPL, K>);
         const dim3 grid(grid_for((ntiles + K - 1) / K, scan_bpc(bpcK, G::TILE_BYTES, r), r.num_cus));
         if (r.dma_aux == 0)
-            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 0, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, a.flags, (scan_burst_kernel<C, MODE, 0, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, a);
         else if (policy == 1)
-            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 18, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, a.flags, (scan_burst_kernel<C, MODE, 18, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, a);
         else if (policy == 2)
-            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 34, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, a.flags, (scan_burst_kernel<C, MODE, 34, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, a);
         else
-            MI355_LAUNCH(r.record, r.scan.flags, (scan_burst_kernel<C, MODE, 2, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, r.scan);
+            MI355_LAUNCH(r.record, a.flags, (scan_burst_kernel<C, MODE, 2, VPL, K>), grid, dim3(kBlockThreads), 0, r.stream, a);
     };
     // "scan_burst" option: 0 = the width's default, 1 = one tile per burst (A/B)
     if (burst_k(C) > 1 && r.scan_burst != 1)

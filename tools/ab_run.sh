@@ -8,7 +8,8 @@ for r in $(seq 1 "$ROUNDS"); do
   for v in old new; do
     cp tools/_ab/libmi355scan_$v.so shared_simd_scan_amd/libmi355scan.so
     echo "== $v (round $r)"
-    bash -c "$CMD"
+    # a failing command ends the A/B: nothing more is started on a GPU that may have faulted
+    bash -c "$CMD" || { rc=$?; cp tools/_ab/libmi355scan_new.so shared_simd_scan_amd/libmi355scan.so; echo "== $v (round $r) failed: rc=$rc"; exit $rc; }
   done
 done
 cp tools/_ab/libmi355scan_new.so shared_simd_scan_amd/libmi355scan.so

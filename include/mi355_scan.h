@@ -83,11 +83,65 @@ MI355_API int mi355_ctx_create(int device, void *hip_stream /* hipStream_t or NU
 MI355_API int mi355_ctx_destroy(mi355_ctx *ctx);
 MI355_API int mi355_ctx_synchronize(mi355_ctx *ctx);
 MI355_API int mi355_device_count(int *count);
-/* re-point the context at another HIP stream (e.g. a capture stream: the *_dev scan / decompress / bitmap entry
- * points enqueue work only -- no allocation, no synchronisation -- so they can be captured into a hipGraph;
- * exceptions: mi355_shared_scan_eq_dev / mi355_scan_in_dev with P > 8 upload the key list per call (asynchronously,
- * through a ring of pinned slots: no stream synchronisation, but refused while the stream is capturing), and
- * mi355_bitmap_to_rowids_dev may grow its workspace) */
+/* ---- Graph capture (hipGraph, torch.cuda.graph): what each device entry point does while the context's stream is capturing.
+ * A capturable call only enqueues work on that stream -- no allocation, no synchronisation, nothing read back -- so it is
+ * recorded as a linear chain of kernel, memset and copy nodes.  Everything passed by value (keys, constants, n, options such
+ * as "grid_cus", and decisions the launcher takes from them: grid, store policy, the "llc_resident_mib" divisor) is frozen
+ * into the nodes; everything behind a device pointer -- columns, masks, row ids, the count mi355_gather_dev reads -- is read
+ * at every replay.  Run each call once outside capture first: a kernel's code is loaded, and its occupancy queried, on first
+ * use.  A call that cannot be captured returns MI355_E_INVALID with a message that names graph capture, enqueues nothing and
+ * leaves the capture intact.  tests/test_graph_capture.py holds every row:
+ *   mi355_dev_alloc              never: synchronises
+ *   mi355_dev_free               never: synchronises
+ *   mi355_dev_upload             never: synchronises
+ *   mi355_dev_download           never: synchronises
+ *   mi355_dev_memset             capturable
+ *   mi355_pack_u16_dev           capturable
+ *   mi355_pack_u32_dev           capturable
+ *   mi355_generate_dev           capturable
+ *   mi355_decompress_dev         capturable
+ *   mi355_scan_eq_dev            capturable
+ *   mi355_scan_range_dev         capturable
+ *   mi355_shared_scan_eq_dev     refused while capturing when P > 8
+ *   mi355_scan_where_dev         capturable
+ *   mi355_scan_combine_dev       capturable
+ *   mi355_shared_scan_where_dev  refused while capturing when P > 8
+ *   mi355_scan_in_dev            refused while capturing when n > 0: every key list is uploaded per call, so the call is
+ *                                never capturable
+ *   mi355_scan2_dev              refused while capturing when the widths differ, bitmap_dev is NULL and the context's
+ *                                buffer pool has to grow
+ *   mi355_scan_select_dev        capturable after a warm-up call of at least this size
+ *   mi355_bitmap_combine_dev     capturable
+ *   mi355_bitmap_count_dev       capturable
+ *   mi355_bitmap_to_rowids_dev   capturable after a warm-up call of at least this size
+ *   mi355_gather_dev             capturable
+ *   mi355_aggregate_dev          capturable
+ *   mi355_histogram_dev          capturable
+ *   mi355_tune_dev               refused while capturing when n >= 5e7 rows (below that it measures nothing and returns)
+ *   mi355_gather_bitmaps_dev     not covered: RCCL collectives need a communicator over several ranks;
+ *                                tests/test_exchange_loopback.py runs them eagerly
+ *   mi355_gather_bitmaps_at_dev  not covered: RCCL collectives need a communicator over several ranks;
+ *                                tests/test_exchange_loopback.py runs them eagerly
+ *   mi355_allreduce_hits_dev     not covered: RCCL collectives need a communicator over several ranks;
+ *                                tests/test_exchange_loopback.py runs them eagerly
+ *   mi355_sharded_scan_eq_dev    not covered: RCCL collectives need a communicator over several ranks;
+ *                                tests/test_exchange_loopback.py runs them eagerly
+ *   mi355_sharded_scan_range_dev not covered: RCCL collectives need a communicator over several ranks;
+ *                                tests/test_exchange_loopback.py runs them eagerly
+ * Key and predicate lists of the shared scans travel in the kernel arguments up to 8 entries; longer ones, and every key list
+ * of mi355_scan_in_dev (its kernel reads the list from device memory only), are uploaded per call (asynchronously,
+ * through a ring of pinned slots: no stream synchronisation) and that copy is what cannot be captured.  "Warm-up of at least
+ * this size": the selection calls keep their look-back state in a workspace of the context that grows with the column (as the
+ * buffer pool behind the two-width count-only mi355_scan2_dev does); growing synchronises and allocates, so it is refused while
+ * capturing -- call once eagerly over a column at least as large.
+ * Lifetime: (1) a graph is valid until its context is destroyed -- a workspace or pool buffer that captured nodes point at is
+ * never freed before mi355_ctx_destroy, even when later eager calls outgrow it; the host-pointer calls, the options and
+ * mi355_ctx_set_stream may be used freely in between.  (2) A graph uses the context's scratch like any call on the context:
+ * the caller orders a replay against the context's current stream (replay on that stream, or make either wait for the other);
+ * two replays, or a replay and an eager call, must never run concurrently.
+ * The Infinity-Cache policy of a repeated scan ("llc_resident_mib" = -1) follows what RUNS back to back: the second of two
+ * identical scans captured into one graph is a repeat, frozen into its node; across the boundary of a capture nothing is. */
+/* re-point the context at another HIP stream, e.g. the stream of a capture that is already under way. */
 /* Scratch, key slots and the buffer pool belong to the context, not to a stream: when neither stream is being captured,
  * work already enqueued on the old stream is ordered before anything enqueued on the new one (event wait, no host
  * synchronisation).  While either stream is capturing the caller orders the two. */
@@ -266,7 +320,8 @@ MI355_API const char *mi355_shared_where_kernel(mi355_ctx *ctx, unsigned c, unsi
 
 /* bitmap[i] = (v_i IN {keys[0..P-1]}) AND (and_mask ? and_mask[i] : 1), negated when `negate` != 0 (NOT IN).
  * 1 <= P <= 1024; keys as in mi355_scan_eq_dev (below c = 32, keys outside [0, 2^c) match nothing).  c <= 16: bitset
- * lookup, cost independent of P; c > 16: compare chain, O(P) per value.  and_mask_dev may be bitmap_dev itself (in place). */
+ * lookup, cost independent of P; c > 16: compare chain, O(P) per value.  and_mask_dev may be bitmap_dev itself (in place).
+ * Every P is uploaded per call; never capturable into a graph (see "Graph capture"). */
 MI355_API int mi355_scan_in_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, const int32_t *keys_host, unsigned P,
                                 int negate, const void *and_mask_dev, void *bitmap_dev, uint64_t *hits_dev);
 
@@ -283,8 +338,8 @@ MI355_API int mi355_scan2_dev(mi355_ctx *ctx, const void *packed1_dev, unsigned 
  *   mask_dev ? COMBINE(p[i], mask[i]) : p[i]        (p, mask_op as in mi355_scan_combine_dev)
  * (at most `capacity` ids are written), count_dev the number of such rows -- ONE launch, and no bitmap ever goes to HBM
  * (the chain scan -> mi355_bitmap_to_rowids_dev writes the bitmap once and reads it twice).  If the in-launch look-back
- * ever gave up waiting (it cannot while the device makes progress) count_dev reads UINT64_MAX.  Not capturable into a
- * graph when the context's workspace has to grow (first call for a larger column). */
+ * ever gave up waiting (it cannot while the device makes progress) count_dev reads UINT64_MAX.  Refused while a graph is
+ * being captured when the context's workspace has to grow (first call for a larger column; see "Graph capture"). */
 MI355_API int mi355_scan_select_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, int op, int64_t a, int64_t b,
                                     int mask_op, const void *mask_dev, uint64_t first_row, uint64_t *rowids_dev, uint64_t capacity,
                                     uint64_t *count_dev);
@@ -299,7 +354,8 @@ MI355_API int mi355_bitmap_combine_dev(mi355_ctx *ctx, int op, const void *a_dev
                                        uint64_t *count_dev);
 MI355_API int mi355_bitmap_count_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t n, uint64_t *count_dev);
 /* selection vector: writes first_row + i for every set bit i < n, ascending, into rowids_dev (at most `capacity`
- * entries are written) and the total number of set bits into count_dev.  workspace: ctx-owned, grows on demand. */
+ * entries are written) and the total number of set bits into count_dev.  workspace: ctx-owned, grows on demand (refused
+ * while a graph is being captured: see "Graph capture"). */
 MI355_API int mi355_bitmap_to_rowids_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t n, uint64_t first_row,
                                          uint64_t *rowids_dev, uint64_t capacity, uint64_t *count_dev);
 

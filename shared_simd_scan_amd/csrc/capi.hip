@@ -77,18 +77,56 @@ int bind(mi355_ctx *ctx)
     return MI355_OK;
 }
 
+// Is `stream` being captured into a graph?  The one capture check of this file.  kCaptureUnknown: the runtime would not say
+// (e.g. the null stream while another stream captures in global mode); whoever is about to synchronise, allocate, free or copy
+// from host memory treats that as kCaptureOn and refuses -- being wrong the other way invalidates somebody's capture.
+// *id (nullable) gets the capture's id, 0 unless kCaptureOn.
+enum CaptureState { kCaptureOff = 0, kCaptureOn = 1, kCaptureUnknown = 2 };
+CaptureState capture_state(hipStream_t stream, unsigned long long *id = nullptr)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    unsigned long long cid = 0;
+    if (id) *id = 0;
+    if (hipStreamGetCaptureInfo(stream, &cap, &cid) != hipSuccess) {
+        (void)hipGetLastError(); // the query's own error is not the caller's to report
+        return kCaptureUnknown;
+    }
+    if (cap == hipStreamCaptureStatusNone) return kCaptureOff;
+    if (id) *id = cid;
+    return kCaptureOn;
+}
+inline CaptureState capture_state(mi355_ctx *ctx, unsigned long long *id = nullptr) { return capture_state(ctx->stream, id); }
+
+// Growing a buffer of the context synchronises, frees and allocates: none of that may happen on a capturing stream (it would
+// invalidate the capture), so it is refused there.  A buffer that a captured node points at (`*in_graph`) is never freed
+// while the context lives -- a graph stays valid until its context is destroyed -- but retired to ctx->retired.
+int grow_buffer(mi355_ctx *ctx, void **buf, size_t *have, bool *in_graph, size_t want, const char *what)
+{
+    if (capture_state(ctx) != kCaptureOff)
+        return fail(MI355_E_INVALID, "%s: workspace must grow: call once outside capture first (graph capture in progress)", what);
+    // whatever still uses the old buffer is ordered on the context's stream
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (*buf) {
+        if (*in_graph)
+            ctx->retired.push_back(*buf);
+        else
+            HIP_TRY(hipFree(*buf));
+    }
+    *buf = nullptr;
+    *have = 0;
+    *in_graph = false;
+    HIP_TRY(hipMalloc(buf, want));
+    *have = want;
+    return MI355_OK;
+}
+
 int pool_get(mi355_ctx *ctx, int slot, size_t bytes, void **out)
 {
     if (ctx->pool_bytes[slot] < bytes) {
-        // whatever still uses the old buffer is ordered on the context's stream
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->pool[slot]) HIP_TRY(hipFree(ctx->pool[slot]));
-        ctx->pool[slot] = nullptr;
-        ctx->pool_bytes[slot] = 0;
         const size_t want = (bytes + (bytes >> 3) + 4095) / 4096 * 4096; // 12 % slack: sizes that creep up do not reallocate each call
-        HIP_TRY(hipMalloc(&ctx->pool[slot], want));
-        ctx->pool_bytes[slot] = want;
+        if (int rc = grow_buffer(ctx, &ctx->pool[slot], &ctx->pool_bytes[slot], &ctx->pool_in_graph[slot], want, "buffer pool")) return rc;
     }
+    if (capture_state(ctx) != kCaptureOff) ctx->pool_in_graph[slot] = true;
     *out = ctx->pool[slot];
     return MI355_OK;
 }
@@ -100,6 +138,19 @@ namespace {
 int check_width(unsigned c)
 {
     if (c < 1 || c > 32) return fail(MI355_E_INVALID, "bit width c=%u outside 1..32", c);
+    return MI355_OK;
+}
+
+// the selection workspace holds at least `entries` words (grown outside capture only; kept alive once a graph points at it)
+int rowid_ws_get(mi355_ctx *ctx, uint64_t entries, const char *what)
+{
+    if (ctx->rowid_ws_entries < entries) {
+        size_t bytes = ctx->rowid_ws_entries * sizeof(unsigned long long);
+        int rc = grow_buffer(ctx, (void **)&ctx->rowid_ws, &bytes, &ctx->rowid_ws_in_graph, entries * sizeof(unsigned long long), what);
+        ctx->rowid_ws_entries = bytes / sizeof(unsigned long long);
+        if (rc) return rc;
+    }
+    if (capture_state(ctx) != kCaptureOff) ctx->rowid_ws_in_graph = true;
     return MI355_OK;
 }
 
@@ -132,10 +183,18 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
     ctx->llc_last_d = -1;
     r.llc_d_out = &ctx->llc_last_d;
     if (r.op == kOpScanEq || r.op == kOpScanRange) {
-        r.llc_repeat = ctx->llc_prev[0] == r.scan.packed && ctx->llc_prev[1] == r.scan.out && ctx->llc_prev[2] == r.scan.and_mask &&
-                       ctx->llc_prev_n == r.scan.n && ctx->llc_prev_c == r.c;
+        // llc_prev is the launch that RUNS directly before this one.  Inside one capture that is the call captured before it
+        // (a graph replays its nodes in the order they were captured); a captured call has not run when the capture ends and
+        // the context never learns when its graph does, so across the boundary of a capture -- an eager call after a captured
+        // one, the first call of a capture, calls of two captures -- nothing is a repeat (llc_prev_capture: the capture's id, 0 = eager).
+        // (One host-side query of the stream's capture state per eq / range scan: no device work, no synchronisation.)
+        unsigned long long cap_id = 0;
+        const bool known = capture_state(ctx, &cap_id) != kCaptureUnknown; // unknown: neither a repeat nor something to repeat
+        r.llc_repeat = known && ctx->llc_prev[0] == r.scan.packed && ctx->llc_prev[1] == r.scan.out && ctx->llc_prev[2] == r.scan.and_mask &&
+                       ctx->llc_prev_n == r.scan.n && ctx->llc_prev_c == r.c && ctx->llc_prev_capture == cap_id;
         ctx->llc_prev[0] = r.scan.packed, ctx->llc_prev[1] = r.scan.out, ctx->llc_prev[2] = r.scan.and_mask;
-        ctx->llc_prev_n = r.scan.n, ctx->llc_prev_c = r.c;
+        ctx->llc_prev_n = r.scan.n, ctx->llc_prev_c = r.c, ctx->llc_prev_capture = cap_id;
+        if (!known) ctx->llc_prev[0] = nullptr;
     } else
         ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
     // the A/B switches of the shared scans (bits 0-8) never reach the selection kernels, whose switches live in bits 9-12 of
@@ -163,12 +222,12 @@ constexpr int kKeySlots = 8;
 // a slot holds the longest list of either kind: 1024 (+ 8 of padding) keys, or as many (lo, span, negate) predicate triples
 constexpr size_t kKeySlotInts = 3 * (kMaxKeys + 8);
 
-// P > 8 keys -> device memory (padded to a multiple of 8 with copies of the last key), asynchronously on the stream
+// keys -> device memory (padded to a multiple of 8 with copies of the last key), asynchronously on the stream: the shared scans'
+// lists of more than 8 keys, and every list of mi355_scan_in_dev
 int upload_keys(mi355_ctx *ctx, const int32_t *keys_host, unsigned P, const int32_t **keys_dev)
 {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(MI355_E_INVALID, "key lists longer than 8 are uploaded per call and cannot be captured into a graph");
+    if (capture_state(ctx) != kCaptureOff)
+        return fail(MI355_E_INVALID, "this key list is uploaded per call (shared scans: P > 8; IN-list: every P) and cannot be captured into a graph");
     const int slot = ctx->key_next;
     ctx->key_next = (slot + 1) % kKeySlots;
     if (ctx->key_used[slot]) HIP_TRY(hipEventSynchronize(ctx->key_events[slot])); // the copy out of this slot is done
@@ -188,8 +247,7 @@ int upload_keys(mi355_ctx *ctx, const int32_t *keys_host, unsigned P, const int3
 // copies of the last: the key ring above, the same rules
 int upload_preds(mi355_ctx *ctx, const uint32_t *triples_host, unsigned P, const uint32_t **preds_dev)
 {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (capture_state(ctx) != kCaptureOff)
         return fail(MI355_E_INVALID, "predicate lists longer than 8 are uploaded per call and cannot be captured into a graph");
     const int slot = ctx->key_next;
     ctx->key_next = (slot + 1) % kKeySlots;
@@ -309,6 +367,7 @@ int mi355_ctx_destroy(mi355_ctx *ctx)
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
     (void)hipFree(ctx->rowid_ws);
     for (int i = 0; i < mi355_ctx::kPoolSlots; i++) (void)hipFree(ctx->pool[i]);
+    for (void *p : ctx->retired) (void)hipFree(p); // buffers a captured graph pointed at: kept until here
     delete ctx;
     return MI355_OK;
 }
@@ -333,10 +392,7 @@ int mi355_ctx_set_stream(mi355_ctx *ctx, void *hip_stream)
     // The scratch, the key slots and the buffer pool belong to the context, not to a stream: work already enqueued on
     // the old stream must be ordered before work on the new one.  A stream that is being captured cannot take part in
     // that (and a captured graph is ordered by whoever launches it): then the caller orders the two streams.
-    hipStreamCaptureStatus c0 = hipStreamCaptureStatusNone, c1 = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(ctx->stream, &c0);
-    (void)hipStreamIsCapturing(next, &c1);
-    if (c0 == hipStreamCaptureStatusNone && c1 == hipStreamCaptureStatusNone && hipStreamQuery(ctx->stream) != hipSuccess) {
+    if (capture_state(ctx->stream) == kCaptureOff && capture_state(next) == kCaptureOff && hipStreamQuery(ctx->stream) != hipSuccess) {
         HIP_TRY(hipEventRecord(ctx->order_event, ctx->stream));
         HIP_TRY(hipStreamWaitEvent(next, ctx->order_event, 0));
     }
@@ -769,14 +825,7 @@ int mi355_scan_select_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, un
     const uint64_t nchunks = (ntiles + select_tiles((int)c) - 1) / select_tiles((int)c);
     // + the chunk-ticket counter on its own line behind them (select_state_words); the same memset zeroes both
     const uint64_t nwords = select_state_words(nchunks);
-    if (ctx->rowid_ws_entries < nwords) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->rowid_ws) HIP_TRY(hipFree(ctx->rowid_ws));
-        ctx->rowid_ws = nullptr;
-        ctx->rowid_ws_entries = 0;
-        HIP_TRY(hipMalloc((void **)&ctx->rowid_ws, nwords * sizeof(unsigned long long)));
-        ctx->rowid_ws_entries = nwords;
-    }
+    if ((rc = rowid_ws_get(ctx, nwords, "mi355_scan_select_dev"))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->rowid_ws, 0, nwords * sizeof(unsigned long long), ctx->stream));
     // the count is written by atomic max (the last chunk's total, or ~0 from a wave that gave up): start it at 0
     HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), ctx->stream));
@@ -945,7 +994,7 @@ int mi355_scan_in_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
         return fail(MI355_E_INVALID, "packed_dev, bitmap_dev and and_mask_dev must be 16-byte aligned");
     if ((rc = bind(ctx))) return rc;
     const int32_t *keys_dev = nullptr;
-    if ((rc = upload_keys(ctx, keys_host, P, &keys_dev))) return rc;
+    if ((rc = upload_keys(ctx, keys_host, P, &keys_dev))) return rc; // every P: in_kernel reads the list from device memory only
     LaunchReq r{};
     r.op = kOpScanIn;
     r.c = c;
@@ -1038,14 +1087,7 @@ int mi355_bitmap_to_rowids_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t 
     g.nchunks = (g.nbytes + kRowidChunk - 1) / kRowidChunk;
     const uint64_t ngroups = (g.nchunks + kRowidScanGroup - 1) / kRowidScanGroup;
     const uint64_t ws_entries = g.nchunks + 1 + ngroups; // chunk counts, the total, one total per scan group
-    if (ctx->rowid_ws_entries < ws_entries) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->rowid_ws) HIP_TRY(hipFree(ctx->rowid_ws));
-        ctx->rowid_ws = nullptr;
-        ctx->rowid_ws_entries = 0;
-        HIP_TRY(hipMalloc((void **)&ctx->rowid_ws, ws_entries * sizeof(unsigned long long)));
-        ctx->rowid_ws_entries = ws_entries;
-    }
+    if ((rc = rowid_ws_get(ctx, ws_entries, "mi355_bitmap_to_rowids_dev"))) return rc;
     g.chunk_counts = ctx->rowid_ws;
     g.rowids = rowids_dev;
     g.capacity = capacity;
@@ -1170,9 +1212,8 @@ int mi355_tune_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned 
     if (what == 0 || (what & ~(unsigned)MI355_TUNE_ALL)) return fail(MI355_E_INVALID, "what=%u: a mask of MI355_TUNE_* bits", what);
     if (n < kTuneMinRows) return MI355_OK; // nothing to learn: such launches never consult the table
     if ((rc = bind(ctx))) return rc;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ctx->stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-        return fail(MI355_E_INVALID, "mi355_tune_dev synchronises: not while the stream is being captured");
+    if (capture_state(ctx) != kCaptureOff)
+        return fail(MI355_E_INVALID, "mi355_tune_dev synchronises: not while the stream is being captured into a graph");
     const size_t stride = mi355_bitmap_stride(n);
     void *bitmaps = nullptr, *values = nullptr;
     if ((rc = pool_get(ctx, mi355_ctx::kPoolOut, 2 * stride, &bitmaps))) return rc;

@@ -11,6 +11,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <vector>
 
 struct mi355_ctx {
     int device = 0;
@@ -32,6 +33,7 @@ struct mi355_ctx {
     int llc_last_d = -1;   // mi355_ctx_last_llc_divisor: ScanArgs::llc_d of the most recent launch, -1 if that was not an eq / range scan
     uint64_t llc_prev_n = 0;
     unsigned llc_prev_c = 0;
+    unsigned long long llc_prev_capture = 0; // id of the graph capture that launch was recorded into, 0 = it ran eagerly (capi.hip launch())
     int dma_aux = 18; // bits 0-3: policy of the HBM->LDS loads (2 = non-temporal: the column is streamed once);
                       // bit 4: non-temporal stores in decompress
     // Every entry point that touches the state below holds `mu` while it does (the host-pointer flavours from their
@@ -52,10 +54,16 @@ struct mi355_ctx {
     hipEvent_t order_event = nullptr;           // mi355_ctx_set_stream: new stream waits for the old one
     unsigned long long *rowid_ws = nullptr;     // chunk counts of mi355_bitmap_to_rowids_dev / mi355_scan_select_dev
     size_t rowid_ws_entries = 0;
+    // Graph capture: a captured memset / kernel node keeps the address of the workspace or pool slot it was recorded with.  A
+    // buffer used under capture is marked; when it has to grow later it is retired (freed in mi355_ctx_destroy) instead of freed,
+    // so a graph stays valid for as long as its context lives.
+    bool rowid_ws_in_graph = false;
+    std::vector<void *> retired;
     // host-pointer (drop-in) flavours: grow-only device buffers kept between calls -- no hipMalloc / hipFree per call
     enum { kPoolIn = 0, kPoolOut = 1, kPoolAux = 2, kPoolSlots = 3 };
     void *pool[kPoolSlots] = {};
     size_t pool_bytes[kPoolSlots] = {};
+    bool pool_in_graph[kPoolSlots] = {};
     bool is_thread_default = false;
     // mi355_ctx_last_launch: the kernels the most recent compute entry point launched (dispatch.hpp note_launch), cleared when
     // the outermost such call starts (host-pointer flavours and compound calls nest)

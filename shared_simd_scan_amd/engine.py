@@ -302,7 +302,8 @@ class ScanEngine:
     def scan_in(self, keys: Sequence[int], col: PackedColumn, negate: bool = False,
                 and_mask: Optional[torch.Tensor] = None, bitmap: Optional[torch.Tensor] = None,
                 hits: Optional[torch.Tensor] = None):
-        """bitmap[i] = value_i in keys (NOT IN with negate=True) [& and_mask[i]]."""
+        """bitmap[i] = value_i in keys (NOT IN with negate=True) [& and_mask[i]].  Every P is uploaded per call; never
+        capturable into a graph (refused while the stream is capturing)."""
         k = keys32(keys, col.c)
         if bitmap is None:
             bitmap = self.alloc_bitmap(col.n)

@@ -5,8 +5,8 @@ equality / range scan and shared multi-predicate scan as hand-written gfx950 HIP
 ABI (include/mi355_scan.h, shared_simd_scan_amd/libmi355scan.so).  See DESIGN.md.
 """
 from ._capi import Mi355Error, lib  # noqa: F401
-from .engine import (PackedColumn, ScanEngine, compressed_buffer_size, decompression_output_buffer_size,  # noqa: F401
+from .engine import (PackedColumn, ScanEngine, clamp_diff, compressed_buffer_size, decompression_output_buffer_size,  # noqa: F401
                      kernel_name, scan_output_buffer_size, shared_where_kernel, tile_values)
 
 __all__ = ["Mi355Error", "PackedColumn", "ScanEngine", "compressed_buffer_size", "decompression_output_buffer_size",
-           "scan_output_buffer_size", "kernel_name", "shared_where_kernel", "tile_values", "lib"]
+           "scan_output_buffer_size", "kernel_name", "shared_where_kernel", "tile_values", "lib", "clamp_diff"]

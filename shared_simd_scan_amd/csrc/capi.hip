@@ -1,4 +1,4 @@
-// capi.hip -- implementation of include/mi355_scan.h (the C ABI of libmi355scan.so).
+// capi.hip -- implementation of include/mi355_scan.h and include/mi355_columns.h (the C ABI of libmi355scan.so).
 //
 // Host-side plumbing only: argument checks, device buffers, stream ordering, kernel dispatch by
 // width.  All arithmetic of the path happens in the HIP kernels of kernels.hpp; there is no CPU
@@ -11,6 +11,8 @@
 
 #include "dispatch.hpp"
 #include "predicates/where_dispatch.hpp"
+#include "predicates/columns_dispatch.hpp"
+#include "../../include/mi355_columns.h"
 #include "extras/gather.hpp"
 #include "kernels.hpp"
 #include "extras/aggregate.hpp"
@@ -282,6 +284,31 @@ int launch_where(mi355_ctx *ctx, WhereReq &r)
     r.w.s.scratch = ctx->kernel_scratch;
     hipError_t e = kWhereGroups[(r.l.c - 1) / 4](r);
     if (e != hipSuccess) return fail(MI355_E_HIP, "kernel launch (shared where-scan, c=%u): %s", r.l.c, hipGetErrorString(e));
+    return MI355_OK;
+}
+
+typedef hipError_t (*columns_group_fn)(const ColumnsReq &);
+const columns_group_fn kColumnsGroups[kNumGroups] = {launch_columns_group_0, launch_columns_group_1, launch_columns_group_2,
+                                                     launch_columns_group_3, launch_columns_group_4, launch_columns_group_5,
+                                                     launch_columns_group_6, launch_columns_group_7};
+
+// as launch_where: no switch word, not tuned per device
+int launch_columns(mi355_ctx *ctx, ColumnsReq &r)
+{
+    if (int rc = bind(ctx)) return rc;
+    r.l.stream = ctx->stream;
+    r.l.device = ctx->device;
+    r.l.num_cus = grid_cus(ctx);
+    r.l.record = &ctx->last_launch;
+    r.l.max_blocks_per_cu = ctx->max_blocks_per_cu;
+    r.k.s.flags = 0;
+    r.k.s.scratch = ctx->kernel_scratch;
+    // bitmap stores as scan2_kernel's: write-through below 768 MiB of bitmap, non-temporal beyond; "scan_nt_stores" overrides
+    r.k.nts = (uint32_t)(ctx->scan_nt_stores < 0 ? (r.k.s.n / 8 > (768ull << 20) ? 1 : 2) : ctx->scan_nt_stores);
+    ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
+    ctx->llc_last_d = -1;
+    hipError_t e = kColumnsGroups[(r.l.c - 1) / 4](r);
+    if (e != hipSuccess) return fail(MI355_E_HIP, "kernel launch (column scan, c1=%u c2=%u): %s", r.l.c, r.k.c2, hipGetErrorString(e));
     return MI355_OK;
 }
 
@@ -895,6 +922,78 @@ int mi355_scan2_dev(mi355_ctx *ctx, const void *packed1_dev, unsigned c1, int op
     r.scan.key2[1] = second.key[1];
     r.scan.invert2 = second.invert;
     return launch(ctx, r);
+}
+
+/* ---- include/mi355_columns.h: a predicate over the row-wise difference of two columns ---- */
+// (op, a, b) over d = v1 - v2 -> an inclusive range [lo, hi] INSIDE the domain of d for this width pair,
+// [-(2^c2 - 1), 2^c1 - 1], and a negation word.  a and b may be any int64: clamped to [-2^33, 2^33] first, which is outside
+// every domain on both sides (no comparison changes) and keeps a - 1 / a + 1 from overflowing.  A range that misses the
+// domain is the full range with the negation flipped, so lo <= hi always and hi - lo <= 2^33 - 2: the kernel needs no
+// encoding of "empty".  Widths up to 30: lo fits an int32 and the span 31 bits (the 32-bit test is exact); above, 64 bits.
+static void fill_difference(ColumnsArgs &k, unsigned c1, unsigned c2, int op, int64_t a, int64_t b)
+{
+    const int64_t dmin = -((1ll << c2) - 1), dmax = (1ll << c1) - 1;
+    const int64_t kLim = 1ll << 33;
+    a = a < -kLim ? -kLim : (a > kLim ? kLim : a);
+    b = b < -kLim ? -kLim : (b > kLim ? kLim : b);
+    int64_t lo = dmin, hi = dmax;
+    bool invert = false;
+    switch (op) {
+    case MI355_CMP_EQ: lo = hi = a; break;
+    case MI355_CMP_NE: lo = hi = a; invert = true; break;
+    case MI355_CMP_LT: hi = a - 1; break;
+    case MI355_CMP_LE: hi = a; break;
+    case MI355_CMP_GT: lo = a + 1; break;
+    case MI355_CMP_GE: lo = a; break;
+    case MI355_CMP_BETWEEN: lo = a; hi = b; break;
+    case MI355_CMP_NOT_BETWEEN: lo = a; hi = b; invert = true; break;
+    }
+    if (lo < dmin) lo = dmin;
+    if (hi > dmax) hi = dmax;
+    if (lo > hi) { // matches no d (or, negated, every d)
+        lo = dmin;
+        hi = dmax;
+        invert = !invert;
+    }
+    k.s.invert = invert ? 0xffffffffu : 0u;
+    k.lo64 = lo;
+    k.span64 = (uint64_t)(hi - lo);
+    k.lo = (uint32_t)(uint64_t)lo;  // two's complement low word: (int32)lo when both widths are <= 30
+    k.span = (uint32_t)(hi - lo);
+}
+
+int mi355_scan_columns_dev(mi355_ctx *ctx, const void *packed1_dev, unsigned c1, const void *packed2_dev, unsigned c2, uint64_t n, int op,
+                           int64_t a, int64_t b, int mask_op, const void *mask_dev, void *bitmap_dev, uint64_t *hits_dev)
+{
+    int rc = resolve(ctx);
+    if (rc) return rc;
+    CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
+    if ((rc = check_width(c1)) || (rc = check_width(c2))) return rc;
+    if (op < MI355_CMP_EQ || op > MI355_CMP_NOT_BETWEEN) return fail(MI355_E_INVALID, "unknown comparison %d", op);
+    if (mask_op < MI355_BITMAP_AND || mask_op > MI355_BITMAP_ANDNOT) return fail(MI355_E_INVALID, "unknown mask op %d", mask_op);
+    if (!bitmap_dev && !hits_dev) return fail(MI355_E_INVALID, "bitmap_dev and hits_dev are both null: nothing to compute");
+    if (n == 0) {
+        if ((rc = bind(ctx))) return rc;
+        if (hits_dev) HIP_TRY(hipMemsetAsync(hits_dev, 0, sizeof(uint64_t), ctx->stream));
+        return MI355_OK;
+    }
+    if (!packed1_dev || !packed2_dev) return fail(MI355_E_INVALID, "null device pointer");
+    if (((uintptr_t)packed1_dev & 15) || ((uintptr_t)packed2_dev & 15) || ((uintptr_t)bitmap_dev & 15) || ((uintptr_t)mask_dev & 15))
+        return fail(MI355_E_INVALID, "packed columns, bitmap_dev and mask_dev must be 16-byte aligned");
+    ColumnsReq r{};
+    r.l.c = c1;
+    r.k.c2 = c2;
+    r.k.s.packed = (const uint8_t *)packed1_dev;
+    r.k.s.packed2 = (const uint8_t *)packed2_dev;
+    r.k.s.n = n;
+    r.k.s.out = (uint8_t *)bitmap_dev;
+    r.k.s.hits = (unsigned long long *)hits_dev;
+    r.k.s.nkeys = 1;
+    r.k.s.and_mask = (const uint8_t *)mask_dev;
+    r.k.s.mask_op = (uint32_t)mask_op;
+    fill_difference(r.k, c1, c2, op, a, b);
+    return launch_columns(ctx, r);
 }
 
 int mi355_scan_where_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned c, int op, int64_t a, int64_t b,

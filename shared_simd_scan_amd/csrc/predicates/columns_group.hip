@@ -1,0 +1,95 @@
+// columns_group.hip -- instantiates scan_columns_kernel (predicates/columns.hpp) for column-1 widths MI355_WLO..MI355_WHI and
+// exports one launcher per group.  Compiled 8 times (4 widths each), like where_group.hip.
+//
+// Per width of column 1: the same-width form, and the run-time-width form with the 32-bit comparison (C1 <= 30 only) and
+// with the 64-bit one -- 94 kernels in all, not 1024.
+#include <atomic>
+
+#include "columns_dispatch.hpp"
+
+#ifndef MI355_WLO
+#error "compile with -DMI355_WLO=<first width> -DMI355_WHI=<last width> -DMI355_GROUP=<index>"
+#endif
+
+namespace mi355 {
+
+template <int C1, int VPL, bool SAME, bool WIDE>
+__global__ __launch_bounds__(kBlockThreads, (columns_occ<C1, VPL, SAME>())) void scan_columns_kernel(ColumnsArgs a)
+{
+    scan_columns_body<C1, VPL, SAME, WIDE>(a);
+}
+
+namespace {
+
+// dynamic LDS beyond the default 64 KiB: raised once per kernel and device
+template <auto Kernel> void allow_dynamic_lds(int max_bytes, int device)
+{
+    static std::atomic<unsigned long long> done{0};
+    const unsigned long long bit = 1ull << (device & 63);
+    if (!(done.load(std::memory_order_acquire) & bit)) {
+        (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
+        done.fetch_or(bit, std::memory_order_release);
+    }
+}
+
+// Blocks per CU.  Both columns in registers: the plain scans' rule on the two tiles together (scan2_kernel: the DMA in
+// flight per CU is what counts, about 40 KiB), inside what LDS and registers admit.  Column 2 read from LDS (32 rows per
+// lane, small tiles, LDS reads all through the decode): as many blocks as fit, up to 4 waves per SIMD.
+template <auto Kernel> int columns_bpc(const ColumnsReq &r, bool same, int tile_bytes, size_t lds)
+{
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, Kernel, kBlockThreads, lds) != hipSuccess || occ < 1) occ = 1;
+    int want = same ? (40 * 1024 + 2 * tile_bytes) / (kWavesPerBlock * tile_bytes) : 4;
+    if (r.l.max_blocks_per_cu > 0) want = r.l.max_blocks_per_cu;
+    if (want < 1) want = 1;
+    if (want > 4) want = 4;
+    return want < occ ? want : occ;
+}
+
+template <int C, int VPL, bool SAME, bool WIDE> hipError_t launch_form(const ColumnsReq &r)
+{
+    using G = ScanGeom<C, VPL>;
+    const uint32_t c2 = r.k.c2;
+    const uint64_t ntiles = (r.k.s.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
+    const size_t lds = columns_block_lds<C, VPL, SAME>(c2);
+    const int tile_bytes = G::TILE_BYTES + (int)(64u * VPL / 8u * c2);
+    allow_dynamic_lds<scan_columns_kernel<C, VPL, SAME, WIDE>>((int)columns_block_lds<C, VPL, SAME>(SAME ? C : 32), r.l.device);
+    // the occupancy query depends on the dynamic LDS, i.e. on c2: asked once per width of column 2
+    static std::atomic<int> bpc_of[33];
+    int occ_bpc = bpc_of[c2].load(std::memory_order_relaxed);
+    if (occ_bpc == 0 || r.l.max_blocks_per_cu > 0) {
+        occ_bpc = columns_bpc<scan_columns_kernel<C, VPL, SAME, WIDE>>(r, SAME, tile_bytes, lds);
+        if (r.l.max_blocks_per_cu <= 0) bpc_of[c2].store(occ_bpc, std::memory_order_relaxed);
+    }
+    const dim3 grid(grid_for(ntiles, occ_bpc, r.l.num_cus));
+    MI355_LAUNCH(r.l.record, 0, (scan_columns_kernel<C, VPL, SAME, WIDE>), grid, dim3(kBlockThreads), lds, r.l.stream, r.k);
+    return hipGetLastError();
+}
+
+template <int C> hipError_t launch_columns(const ColumnsReq &r)
+{
+    const uint32_t c2 = r.k.c2;
+    if (c2 == (uint32_t)C) return launch_form<C, columns_vpl(C, true), true, (C > 30)>(r);
+    if constexpr (C <= 30) {
+        if (c2 <= 30) return launch_form<C, columns_vpl(C, false), false, false>(r);
+    }
+    return launch_form<C, columns_vpl(C, false), false, true>(r);
+}
+
+template <int C> hipError_t launch_columns_from(const ColumnsReq &r)
+{
+    if (r.l.c == C) return launch_columns<C>(r);
+    if constexpr (C < MI355_WHI)
+        return launch_columns_from<C + 1>(r);
+    else
+        return hipErrorInvalidValue;
+}
+
+} // namespace
+
+#define MI355_CAT2(a, b) a##b
+#define MI355_CAT(a, b) MI355_CAT2(a, b)
+
+hipError_t MI355_CAT(launch_columns_group_, MI355_GROUP)(const ColumnsReq &r) { return launch_columns_from<MI355_WLO>(r); }
+
+} // namespace mi355

@@ -54,6 +54,12 @@ def clamp_const(x: int) -> int:
     return min(max(int(x), -1), 1 << 32)
 
 
+def clamp_diff(x: int) -> int:
+    """a comparison constant of scan_columns (any int) -> [-2^32, 2^32]: the difference of two decoded values lies strictly
+    inside that range, so this changes no comparison, and the result fits c_int64"""
+    return min(max(int(x), -(1 << 32)), 1 << 32)
+
+
 def range_bounds(lo: int, hi: int) -> Optional[Tuple[int, int]]:
     """scan_range's inclusive bounds (any ints) -> (lo, hi) within [0, 2^32), or None when no value can lie in between
     (the rules of the C++ drop-in scan(int, int) in include/simd_scan.hpp, extended to ints beyond 32 bits)"""
@@ -286,6 +292,22 @@ class ScanEngine:
         check(lib().mi355_scan2_dev(self._ctx, col1.data.data_ptr(), col1.c, self._CMP[op1], clamp_const(a1), clamp_const(b1),
                                     col2.data.data_ptr(), col2.c, self._CMP[op2], clamp_const(a2), clamp_const(b2), col1.n, self._BOP[combine],
                                     None if count_only else bitmap.data_ptr(), hits.data_ptr()))
+        return (None if count_only else bitmap), hits
+
+    def scan_columns(self, col1: PackedColumn, op: str, col2: PackedColumn, a: int = 0, b: int = 0, mask: Optional[torch.Tensor] = None,
+                     mask_op: str = "and", bitmap: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None,
+                     count_only: bool = False):
+        """bitmap[i] = (col1_i - col2_i) OP a [, b], the exact integer difference of the two rows: col1 < col2 is ("<", a=0),
+        col1 >= col2 + 30 is (">=", a=30), |col1 - col2| <= 3 is ("between", a=-3, b=3).  Any width pair, one launch; mask,
+        mask_op, bitmap, hits and count_only as in scan_combine."""
+        assert col1.n == col2.n
+        if bitmap is None and not count_only:
+            bitmap = self.alloc_bitmap(col1.n)
+        if hits is None:
+            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        check(lib().mi355_scan_columns_dev(self._ctx, col1.data.data_ptr(), col1.c, col2.data.data_ptr(), col2.c, col1.n, self._CMP[op],
+                                           clamp_diff(a), clamp_diff(b), self._BOP[mask_op], mask.data_ptr() if mask is not None else None,
+                                           None if count_only else bitmap.data_ptr(), hits.data_ptr()))
         return (None if count_only else bitmap), hits
 
     def scan_select(self, op: str, a: int, col: PackedColumn, capacity: int, b: int = 0, mask: Optional[torch.Tensor] = None,

@@ -18,9 +18,25 @@
  *     first (src/simd_scan_compression.cpp:53-104).  A packed buffer must be at least
  *     mi355_compressed_buffer_size(c, n) bytes (payload + 256 B pad, src/simd_scan.hpp:20-26);
  *     device packed buffers must be 16-byte aligned.
+ *   - what lies behind value n-1: ANYTHING.  The pad, and the bits of the last payload byte behind value n-1, need not be
+ *     zero and never reach a result -- a packed_dev may point into the middle of a longer column (a row range that starts
+ *     on a whole value at the alignment below), followed by that column's next rows.  The bytes must be readable.
  *   - bitmap format: bit i = byte i/8, bit i%8 (src/util.cpp:51-58).  The engine writes exactly
  *     ceil(n/8) bytes; bits >= n of the last byte are 0; hits = popcount over [0, n).  (The
- *     reference's variants disagree with each other past n; see DESIGN.md "tail rule".)
+ *     reference's variants disagree with each other past n; see DESIGN.md "tail rule".)  A bitmap passed IN (mask_dev,
+ *     and_mask_dev, a_dev / b_dev, bitmap_dev of the consumers) must be canonical -- bits >= n of its last byte 0 -- and is
+ *     read up to ceil(n/8) bytes and no further: what lies behind it may hold anything.
+ *   - minimum alignment of device pointers (a misaligned one is MI355_E_INVALID, nothing is launched), by argument:
+ *       16 bytes: packed_dev / packed1_dev / packed2_dev, bitmap_dev, mask_dev / and_mask_dev, a_dev / b_dev / out_dev of
+ *                 mi355_bitmap_combine_dev, bitmap_dev of mi355_bitmap_count_dev, out_dev of the shared scans (and their
+ *                 stride_bytes), out_dev of mi355_decompress_dev -- except:
+ *        4 bytes: bitmap_dev of mi355_bitmap_to_rowids_dev, packed_dev of mi355_gather_dev (a row range that starts at a
+ *                 multiple of 32 rows), mask_dev of mi355_aggregate_dev / mi355_histogram_dev, packed_dev (the
+ *                 destination) of mi355_pack_u16_dev / mi355_pack_u32_dev / mi355_generate_dev;
+ *       natural alignment of their element type: hits_dev, count_dev, rowids_dev, counts_dev, values_dev and the int32 /
+ *                 uint64 outputs of mi355_gather_dev / mi355_aggregate_dev / mi355_histogram_dev.
+ *     Nothing more is needed: no entry point asks for 32-, 64- or 128-byte alignment (mi355_bitmap_stride is a speed
+ *     recommendation).  tests/test_min_contract.py runs every device entry point at exactly these alignments.
  *   - keys are signed 32-bit and compared unmasked as their unsigned 32-bit pattern: below c = 32 a key outside
  *     [0, 2^c) -- a negative one included -- matches nothing (reference behaviour, SURVEY 8c hazard 5); at c = 32
  *     every pattern is a value, so key -1 matches 0xffffffff and key INT32_MIN matches 0x80000000.

@@ -10,6 +10,8 @@
 #include <vector>
 
 #include "dispatch.hpp"
+#include "launch_util.hpp"
+#include "shared_plan.hpp"
 #include "predicates/where_dispatch.hpp"
 #include "predicates/columns_dispatch.hpp"
 #include "../../include/mi355_columns.h"
@@ -156,9 +158,9 @@ int rowid_ws_get(mi355_ctx *ctx, uint64_t entries, const char *what)
     return MI355_OK;
 }
 
-typedef hipError_t (*group_fn)(const LaunchReq &);
-const group_fn kGroups[kNumGroups] = {launch_group_0, launch_group_1, launch_group_2, launch_group_3,
-                                      launch_group_4, launch_group_5, launch_group_6, launch_group_7};
+hipError_t (*const kGroups[kNumGroups])(const LaunchReq &) = MI355_GROUP_TABLE(launch_group_);
+hipError_t (*const kWhereGroups[kNumGroups])(const WhereReq &) = MI355_GROUP_TABLE(launch_where_group_);
+hipError_t (*const kColumnsGroups[kNumGroups])(const ColumnsReq &) = MI355_GROUP_TABLE(launch_columns_group_);
 
 // rows from which a launch uses what mi355_tune_dev measured (smaller columns take microseconds whatever the grid)
 constexpr uint64_t kTuneMinRows = 50000000ull;
@@ -169,16 +171,22 @@ inline uint32_t tune_key(int op, unsigned c, bool writes_bitmap, bool reads_mask
     return (uint32_t)op * 64u + c + (writes_bitmap ? 0u : 1u << 12) + (reads_mask ? 1u << 13 : 0u);
 }
 
+// what every launcher's request takes from the context (LaunchReq, WhereReq::l, ColumnsReq::l)
+void fill_common(mi355_ctx *ctx, LaunchReq &l)
+{
+    l.stream = ctx->stream;
+    l.device = ctx->device;
+    l.num_cus = grid_cus(ctx);
+    l.record = l.choice_out ? nullptr : &ctx->last_launch; // introspection stays out of the record
+    l.max_blocks_per_cu = ctx->max_blocks_per_cu;
+    l.scan_nt_stores = ctx->scan_nt_stores;
+}
+
 int launch(mi355_ctx *ctx, LaunchReq &r)
 {
     if (int rc = bind(ctx)) return rc;
-    r.stream = ctx->stream;
-    r.device = ctx->device;
-    r.num_cus = grid_cus(ctx);
-    r.record = &ctx->last_launch;
-    r.max_blocks_per_cu = ctx->max_blocks_per_cu;
+    fill_common(ctx, r);
     r.dma_aux = ctx->dma_aux;
-    r.scan_nt_stores = ctx->scan_nt_stores;
     r.shared_vpl = ctx->shared_vpl;
     r.scan_burst = ctx->scan_burst;
     r.llc_resident_mib = ctx->llc_resident_mib;
@@ -224,62 +232,46 @@ constexpr int kKeySlots = 8;
 // a slot holds the longest list of either kind: 1024 (+ 8 of padding) keys, or as many (lo, span, negate) predicate triples
 constexpr size_t kKeySlotInts = 3 * (kMaxKeys + 8);
 
-// keys -> device memory (padded to a multiple of 8 with copies of the last key), asynchronously on the stream: the shared scans'
-// lists of more than 8 keys, and every list of mi355_scan_in_dev
+// A list of P elements of elem_bytes -> device memory, padded to a multiple of 8 elements with copies of the last,
+// asynchronously on the stream, through the ring of kKeySlots pinned / device slots.  `what`: the refusal under capture.
+int upload_list(mi355_ctx *ctx, const void *src, size_t elem_bytes, unsigned P, const char *what, const void **dev)
+{
+    if (capture_state(ctx) != kCaptureOff) return fail(MI355_E_INVALID, "%s", what);
+    const int slot = ctx->key_next;
+    ctx->key_next = (slot + 1) % kKeySlots;
+    if (ctx->key_used[slot]) HIP_TRY(hipEventSynchronize(ctx->key_events[slot])); // the copy out of this slot is done
+    uint8_t *h = (uint8_t *)(ctx->keys_pinned + (size_t)slot * kKeySlotInts);
+    uint8_t *d = (uint8_t *)(ctx->keys_scratch + (size_t)slot * kKeySlotInts);
+    const unsigned npad = (P + 7) / 8 * 8;
+    memcpy(h, src, (size_t)P * elem_bytes);
+    for (unsigned k = P; k < npad; k++) memcpy(h + k * elem_bytes, (const uint8_t *)src + (size_t)(P - 1) * elem_bytes, elem_bytes);
+    HIP_TRY(hipMemcpyAsync(d, h, (size_t)npad * elem_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->key_events[slot], ctx->stream));
+    ctx->key_used[slot] = true;
+    *dev = d;
+    return MI355_OK;
+}
+
+// keys: the shared scans' lists of more than 8 keys, and every list of mi355_scan_in_dev
 int upload_keys(mi355_ctx *ctx, const int32_t *keys_host, unsigned P, const int32_t **keys_dev)
 {
-    if (capture_state(ctx) != kCaptureOff)
-        return fail(MI355_E_INVALID, "this key list is uploaded per call (shared scans: P > 8; IN-list: every P) and cannot be captured into a graph");
-    const int slot = ctx->key_next;
-    ctx->key_next = (slot + 1) % kKeySlots;
-    if (ctx->key_used[slot]) HIP_TRY(hipEventSynchronize(ctx->key_events[slot])); // the copy out of this slot is done
-    int32_t *h = ctx->keys_pinned + (size_t)slot * kKeySlotInts;
-    int32_t *d = ctx->keys_scratch + (size_t)slot * kKeySlotInts;
-    const unsigned npad = (P + 7) / 8 * 8;
-    memcpy(h, keys_host, P * sizeof(int32_t));
-    for (unsigned k = P; k < npad; k++) h[k] = keys_host[P - 1];
-    HIP_TRY(hipMemcpyAsync(d, h, npad * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->key_events[slot], ctx->stream));
-    ctx->key_used[slot] = true;
-    *keys_dev = d;
-    return MI355_OK;
+    return upload_list(ctx, keys_host, sizeof(int32_t), P,
+                       "this key list is uploaded per call (shared scans: P > 8; IN-list: every P) and cannot be captured into a graph",
+                       (const void **)keys_dev);
 }
 
-// P > 8 normalised predicates -> device memory as (lo, span, negate) triples, padded to a multiple of 8 predicates with
-// copies of the last: the key ring above, the same rules
+// P > 8 normalised predicates as (lo, span, negate) triples
 int upload_preds(mi355_ctx *ctx, const uint32_t *triples_host, unsigned P, const uint32_t **preds_dev)
 {
-    if (capture_state(ctx) != kCaptureOff)
-        return fail(MI355_E_INVALID, "predicate lists longer than 8 are uploaded per call and cannot be captured into a graph");
-    const int slot = ctx->key_next;
-    ctx->key_next = (slot + 1) % kKeySlots;
-    if (ctx->key_used[slot]) HIP_TRY(hipEventSynchronize(ctx->key_events[slot])); // the copy out of this slot is done
-    uint32_t *h = (uint32_t *)(ctx->keys_pinned + (size_t)slot * kKeySlotInts);
-    uint32_t *d = (uint32_t *)(ctx->keys_scratch + (size_t)slot * kKeySlotInts);
-    const unsigned npad = (P + 7) / 8 * 8;
-    memcpy(h, triples_host, (size_t)P * 3 * sizeof(uint32_t));
-    for (unsigned k = P; k < npad; k++) memcpy(h + 3 * k, triples_host + 3 * (P - 1), 3 * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(d, h, (size_t)npad * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->key_events[slot], ctx->stream));
-    ctx->key_used[slot] = true;
-    *preds_dev = d;
-    return MI355_OK;
+    return upload_list(ctx, triples_host, 3 * sizeof(uint32_t), P,
+                       "predicate lists longer than 8 are uploaded per call and cannot be captured into a graph", (const void **)preds_dev);
 }
-
-typedef hipError_t (*where_group_fn)(const WhereReq &);
-const where_group_fn kWhereGroups[kNumGroups] = {launch_where_group_0, launch_where_group_1, launch_where_group_2, launch_where_group_3,
-                                                 launch_where_group_4, launch_where_group_5, launch_where_group_6, launch_where_group_7};
 
 // the kernels of predicates/ take no switch word (their launch records read flags=0x0) and are not tuned per device
 int launch_where(mi355_ctx *ctx, WhereReq &r)
 {
     if (int rc = bind(ctx)) return rc;
-    r.l.stream = ctx->stream;
-    r.l.device = ctx->device;
-    r.l.num_cus = grid_cus(ctx);
-    r.l.record = &ctx->last_launch;
-    r.l.max_blocks_per_cu = ctx->max_blocks_per_cu;
-    r.l.scan_nt_stores = ctx->scan_nt_stores;
+    fill_common(ctx, r.l);
     r.w.s.flags = 0;
     r.w.s.scratch = ctx->kernel_scratch;
     hipError_t e = kWhereGroups[(r.l.c - 1) / 4](r);
@@ -287,24 +279,15 @@ int launch_where(mi355_ctx *ctx, WhereReq &r)
     return MI355_OK;
 }
 
-typedef hipError_t (*columns_group_fn)(const ColumnsReq &);
-const columns_group_fn kColumnsGroups[kNumGroups] = {launch_columns_group_0, launch_columns_group_1, launch_columns_group_2,
-                                                     launch_columns_group_3, launch_columns_group_4, launch_columns_group_5,
-                                                     launch_columns_group_6, launch_columns_group_7};
-
 // as launch_where: no switch word, not tuned per device
 int launch_columns(mi355_ctx *ctx, ColumnsReq &r)
 {
     if (int rc = bind(ctx)) return rc;
-    r.l.stream = ctx->stream;
-    r.l.device = ctx->device;
-    r.l.num_cus = grid_cus(ctx);
-    r.l.record = &ctx->last_launch;
-    r.l.max_blocks_per_cu = ctx->max_blocks_per_cu;
+    fill_common(ctx, r.l);
     r.k.s.flags = 0;
     r.k.s.scratch = ctx->kernel_scratch;
     // bitmap stores as scan2_kernel's: write-through below 768 MiB of bitmap, non-temporal beyond; "scan_nt_stores" overrides
-    r.k.nts = (uint32_t)(ctx->scan_nt_stores < 0 ? (r.k.s.n / 8 > (768ull << 20) ? 1 : 2) : ctx->scan_nt_stores);
+    r.k.nts = (uint32_t)one_pass_store_policy(r.k.s.n / 8, ctx->scan_nt_stores);
     ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
     ctx->llc_last_d = -1;
     hipError_t e = kColumnsGroups[(r.l.c - 1) / 4](r);
@@ -1562,9 +1545,7 @@ const char *mi355_shared_scan_kernel(mi355_ctx *ctx, unsigned c, unsigned P, int
     r.scan.layout = (uint32_t)layout;
     r.scan.hits = with_hits ? &dummy : nullptr;
     if (launch(ctx, r) != MI355_OK) return nullptr;
-    static const char *const names[] = {"shared_lut_kernel", "shared_lut_kernel(multi-pass)", "shared_wide_kernel", "shared_general_kernel",
-                                        "shared_linear_kernel", "shared_pair_kernel"};
-    return choice >= 0 && choice < 6 ? names[choice] : nullptr;
+    return choice >= 0 && choice < 6 ? kSharedFamilyName[choice] : nullptr;
 }
 
 const char *mi355_shared_where_kernel(mi355_ctx *ctx, unsigned c, unsigned P, int layout, int with_hits)

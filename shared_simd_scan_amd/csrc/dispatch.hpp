@@ -64,10 +64,12 @@ inline void note_launch(std::string *rec, const std::string &label, const dim3 &
 }
 
 // hipLaunchKernelGGL + the launch record.  FLAGS: the ScanArgs::flags word the kernel receives (0 for kernels without one).
-#define MI355_LAUNCH(REC, FLAGS, KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                                      \
+// REQ: a LaunchReq -- recorded in its `record`; with `choice_out` set (a dry run) NOTHING is launched -- or, for the
+// launchers that have no request, the record itself (std::string *, may be null).
+#define MI355_LAUNCH(REQ, FLAGS, KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                                      \
     do {                                                                                                                   \
-        ::mi355::note_launch((REC), ::mi355::kernel_label<KERNEL>(), dim3(GRID), (size_t)(LDS), (uint32_t)(FLAGS));       \
-        hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                                                 \
+        ::mi355::note_launch(::mi355::record_of(REQ), ::mi355::kernel_label<KERNEL>(), dim3(GRID), (size_t)(LDS), (uint32_t)(FLAGS)); \
+        if (!::mi355::dry_run(REQ)) hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                     \
     } while (0)
 
 enum Op { kOpScanEq = 0, kOpScanRange = 1, kOpSharedScan = 2, kOpDecompress = 3, kOpScanIn = 4, kOpSelect = 5, kOpScan2 = 6 };
@@ -88,11 +90,19 @@ struct LaunchReq {
     int select_single;     // kOpSelect: 1 = the older single-role kernel (option "select_kernel" = 1, A/B), 0 = decoder / expander roles
     int shared_vpl;        // shared scans of <= 8 keys: values per lane and tile, 0 = the engine's choice, 64, 128 (c <= 12)
     std::string *record;   // the context's launch record (mi355_ctx_last_launch), null = not recorded
-    int *choice_out;       // kOpSharedScan: non-null = only report the kernel family that would run (0 one-pass LUT,
-                           // 1 byte-entry multi-pass LUT, 2 dword-entry LUT, 3 compare chain), launch nothing
+    int *choice_out;       // introspection, the same in every group (width, where, columns): non-null = a dry run.  Nothing is
+                           // launched (MI355_LAUNCH sees to it); the kernel family goes to *choice_out -- shared scans: a
+                           // SharedFamily (shared_plan.hpp: one-pass LUT, byte-entry multi-pass LUT, 32 keys per lookup, compare
+                           // chain, linear rows, pair), where-scans: a WhereChoice, every other op has one family and reports
+                           // none -- and `record`, if set, gets the line the launch would have written
     ScanArgs scan;
     DecompArgs decomp;
 };
+
+inline std::string *record_of(std::string *rec) { return rec; }
+inline std::string *record_of(const LaunchReq &r) { return r.record; }
+inline bool dry_run(std::string *) { return false; }
+inline bool dry_run(const LaunchReq &r) { return r.choice_out != nullptr; }
 
 // Persistent grid: at most (resident blocks per CU) x (CUs) blocks of 4 waves; each wave strides
 // over the wave tiles.  Small inputs get one wave per tile.
@@ -105,13 +115,11 @@ inline unsigned grid_for(uint64_t ntiles, int blocks_per_cu, int num_cus)
 }
 
 constexpr int kNumGroups = 8; // widths 1..32, 4 per group
-hipError_t launch_group_0(const LaunchReq &);
-hipError_t launch_group_1(const LaunchReq &);
-hipError_t launch_group_2(const LaunchReq &);
-hipError_t launch_group_3(const LaunchReq &);
-hipError_t launch_group_4(const LaunchReq &);
-hipError_t launch_group_5(const LaunchReq &);
-hipError_t launch_group_6(const LaunchReq &);
-hipError_t launch_group_7(const LaunchReq &);
+// the eight group launchers of a family of translation units (STEM##0 .. STEM##7): their declarations, and their table
+#define MI355_DECLARE_GROUPS(STEM, REQ)                                                                                     \
+    hipError_t STEM##0(const REQ &), STEM##1(const REQ &), STEM##2(const REQ &), STEM##3(const REQ &), STEM##4(const REQ &), \
+        STEM##5(const REQ &), STEM##6(const REQ &), STEM##7(const REQ &)
+#define MI355_GROUP_TABLE(STEM) {STEM##0, STEM##1, STEM##2, STEM##3, STEM##4, STEM##5, STEM##6, STEM##7}
+MI355_DECLARE_GROUPS(launch_group_, LaunchReq);
 
 } // namespace mi355

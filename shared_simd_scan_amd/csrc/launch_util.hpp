@@ -1,0 +1,108 @@
+// launch_util.hpp -- the host-side launch helpers that capi.hip and the three group translation units (width_group.hip,
+// predicates/where_group.hip, predicates/columns_group.hip) share: one copy of each.  No device code.
+#pragma once
+
+#include <atomic>
+#include <type_traits>
+
+#include "dispatch.hpp"
+
+namespace mi355 {
+
+template <typename K> int blocks_per_cu(K kernel)
+{
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlockThreads, 0) != hipSuccess || nb < 1) nb = 1;
+    return nb;
+}
+
+// Kernels that take their lookup tables as dynamic LDS may need more than the default 64 KiB: raise the limit once
+// per kernel AND device (the attribute is per device; a process may hold contexts on several GPUs).
+template <auto Kernel> void allow_dynamic_lds(int max_bytes, int device)
+{
+    static std::atomic<unsigned long long> done{0};
+    const unsigned long long bit = 1ull << (device & 63);
+    if (!(done.load(std::memory_order_acquire) & bit)) {
+        (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
+        done.fetch_or(bit, std::memory_order_release);
+    }
+}
+
+// option "max_blocks_per_cu" (0 = no cap) on top of what a kernel admits
+inline int cap_bpc(int bpc, int max_blocks_per_cu) { return (max_blocks_per_cu > 0 && max_blocks_per_cu < bpc) ? max_blocks_per_cu : bpc; }
+
+// Blocks per CU the streaming scans want (the launcher takes the smaller of this and what the occupancy query admits).
+// Measured on MI355X (tools/sweep.py, 1e9 rows): the scans run fastest with ~36-48 KiB of LDS-DMA in flight per CU -- one
+// 4-wave block at c=9 (4 x 9 KiB tiles) -- and lose 3-6 % at the occupancy limit (more concurrent streams, same bytes).
+// So: the number of blocks whose tiles add up to ~40 KiB, at least 1.
+inline int scan_want_bpc(int tile_bytes, int max_blocks_per_cu)
+{
+    if (max_blocks_per_cu > 0) return max_blocks_per_cu;
+    int want = (40 * 1024 + 2 * tile_bytes) / (kWavesPerBlock * tile_bytes); // rounded
+    if (want < 1) want = 1;
+    if (want > 4) want = 4; // c = 1, 2 (1-2 KiB tiles): four blocks per CU beat eight by 20 % / 6 % (launches back to back)
+    return want;
+}
+
+// ---- store policies: `scan_nt_stores` is the option (-1 = by size), `out_bytes` what the launch writes ------------------
+
+// Kernels that write every output byte once, in one pass (the eq / range scans, in_kernel, scan2_kernel, the column scan,
+// the pair kernel and the one-pass LUT kernels): 0 plain, 1 non-temporal, 2 write-through (sc1).
+// Bitmap stores, measured with launches back to back (bench.py --store-policy, same box, 1e9 x 9 bit unless noted):
+// write-through (sc1) 0.201 ms, plain 0.207, non-temporal 0.216 -- dirty bitmap lines do not pile up in L2 to be
+// written back under the next launch's read stream; c = 21: 0.438 / 0.467 / 0.457; c = 5: 0.127 / 0.129 / 0.136.
+// Bitmaps far beyond the 256 MiB Infinity Cache prefer non-temporal stores: 4e9 rows sc1 0.82 ms / nt 0.85,
+// 8e9 rows (1 GB of bitmap) 1.74 / 1.72.
+// The one-pass shared scans follow (launches back to back, P = 8: 1e8 rows sc1 0.046 ms / plain 0.047 / nt 0.049; 1e9 rows
+// nt 0.353-0.383 / sc1 0.347-0.393 / plain 0.40).
+inline int one_pass_store_policy(uint64_t out_bytes, int scan_nt_stores)
+{
+    return scan_nt_stores < 0 ? (out_bytes > (768ull << 20) ? 1 : 2) : scan_nt_stores;
+}
+
+// The multi-pass shared scans of more than 8 keys / predicates: non-temporal result stores unless the P bitmaps together
+// are small.  Measured (tools/sweep.py --nts 0,1, P = 8, c = 9): 1e8 rows (100 MB of bitmaps) 0.0540 -> 0.0525 ms, 5e8
+// 0.220 -> 0.214, 1e9 0.409 -> 0.372; c = 17: -1..-4 %.  Unlike the single bitmap of the plain scans, these outputs gain
+// nothing from staying in the Infinity Cache.
+inline bool multi_pass_nt_stores(uint64_t out_bytes, int scan_nt_stores)
+{
+    return scan_nt_stores < 0 ? out_bytes > (64ull << 20) : scan_nt_stores != 0;
+}
+
+// ---- compile-time fan-out ------------------------------------------------------------------------------------------------
+
+// The width ladder of a group translation unit: f(std::integral_constant<int, C>{}, r) for the C in LO .. HI that c names.
+template <int LO, int HI, typename Req, typename F> hipError_t launch_by_width(unsigned c, const Req &r, F f)
+{
+    if (c == (unsigned)LO) return f(std::integral_constant<int, LO>{}, r);
+    if constexpr (LO < HI)
+        return launch_by_width<LO + 1, HI>(c, r, f);
+    else
+        return hipErrorInvalidValue;
+}
+
+// launch_group_3, launch_where_group_3, ...: MI355_CAT(launch_group_, MI355_GROUP)
+#define MI355_CAT2(a, b) a##b
+#define MI355_CAT(a, b) MI355_CAT2(a, b)
+
+// A run-time (rc, big) pair as template arguments: f(std::integral_constant<int, rc>{}, std::bool_constant<big>{}).
+// Only what a kernel can use is instantiated: rc counts as 0 unless kMaxRc is 2, and BIG = true exists at kBigWidth widths only.
+template <int kMaxRc, bool kBigWidth, typename F> void with_rc_big(int rc, bool big, F f)
+{
+    auto with_big = [&](auto rc_c) {
+        if constexpr (kBigWidth) {
+            if (big) return f(rc_c, std::true_type{});
+        }
+        f(rc_c, std::false_type{});
+    };
+    if constexpr (kMaxRc >= 2) {
+        if (rc == 1) return with_big(std::integral_constant<int, 1>{});
+        if (rc == 2) return with_big(std::integral_constant<int, 2>{});
+    }
+    with_big(std::integral_constant<int, 0>{});
+}
+
+// what a launcher returns: in a dry run (LaunchReq::choice_out) nothing was launched, so nothing can have failed
+inline hipError_t launch_status(const LaunchReq &r) { return r.choice_out ? hipSuccess : hipGetLastError(); }
+
+} // namespace mi355

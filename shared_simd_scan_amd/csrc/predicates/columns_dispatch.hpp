@@ -12,13 +12,6 @@ struct ColumnsReq {
     ColumnsArgs k; // what the kernel receives
 };
 
-hipError_t launch_columns_group_0(const ColumnsReq &);
-hipError_t launch_columns_group_1(const ColumnsReq &);
-hipError_t launch_columns_group_2(const ColumnsReq &);
-hipError_t launch_columns_group_3(const ColumnsReq &);
-hipError_t launch_columns_group_4(const ColumnsReq &);
-hipError_t launch_columns_group_5(const ColumnsReq &);
-hipError_t launch_columns_group_6(const ColumnsReq &);
-hipError_t launch_columns_group_7(const ColumnsReq &);
+MI355_DECLARE_GROUPS(launch_columns_group_, ColumnsReq);
 
 } // namespace mi355

@@ -5,6 +5,7 @@
 // with the 64-bit one -- 94 kernels in all, not 1024.
 #include <atomic>
 
+#include "../launch_util.hpp"
 #include "columns_dispatch.hpp"
 
 #ifndef MI355_WLO
@@ -20,17 +21,6 @@ __global__ __launch_bounds__(kBlockThreads, (columns_occ<C1, VPL, SAME>())) void
 }
 
 namespace {
-
-// dynamic LDS beyond the default 64 KiB: raised once per kernel and device
-template <auto Kernel> void allow_dynamic_lds(int max_bytes, int device)
-{
-    static std::atomic<unsigned long long> done{0};
-    const unsigned long long bit = 1ull << (device & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
-        done.fetch_or(bit, std::memory_order_release);
-    }
-}
 
 // Blocks per CU.  Both columns in registers: the plain scans' rule on the two tiles together (scan2_kernel: the DMA in
 // flight per CU is what counts, about 40 KiB), inside what LDS and registers admit.  Column 2 read from LDS (32 rows per
@@ -62,8 +52,8 @@ template <int C, int VPL, bool SAME, bool WIDE> hipError_t launch_form(const Col
         if (r.l.max_blocks_per_cu <= 0) bpc_of[c2].store(occ_bpc, std::memory_order_relaxed);
     }
     const dim3 grid(grid_for(ntiles, occ_bpc, r.l.num_cus));
-    MI355_LAUNCH(r.l.record, 0, (scan_columns_kernel<C, VPL, SAME, WIDE>), grid, dim3(kBlockThreads), lds, r.l.stream, r.k);
-    return hipGetLastError();
+    MI355_LAUNCH(r.l, 0, (scan_columns_kernel<C, VPL, SAME, WIDE>), grid, dim3(kBlockThreads), lds, r.l.stream, r.k);
+    return launch_status(r.l);
 }
 
 template <int C> hipError_t launch_columns(const ColumnsReq &r)
@@ -76,20 +66,11 @@ template <int C> hipError_t launch_columns(const ColumnsReq &r)
     return launch_form<C, columns_vpl(C, false), false, true>(r);
 }
 
-template <int C> hipError_t launch_columns_from(const ColumnsReq &r)
-{
-    if (r.l.c == C) return launch_columns<C>(r);
-    if constexpr (C < MI355_WHI)
-        return launch_columns_from<C + 1>(r);
-    else
-        return hipErrorInvalidValue;
-}
-
 } // namespace
 
-#define MI355_CAT2(a, b) a##b
-#define MI355_CAT(a, b) MI355_CAT2(a, b)
-
-hipError_t MI355_CAT(launch_columns_group_, MI355_GROUP)(const ColumnsReq &r) { return launch_columns_from<MI355_WLO>(r); }
+hipError_t MI355_CAT(launch_columns_group_, MI355_GROUP)(const ColumnsReq &r)
+{
+    return launch_by_width<MI355_WLO, MI355_WHI>(r.l.c, r, [](auto c, const ColumnsReq &q) { return launch_columns<decltype(c)::value>(q); });
+}
 
 } // namespace mi355

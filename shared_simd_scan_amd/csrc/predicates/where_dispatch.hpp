@@ -15,13 +15,6 @@ struct WhereReq {
     WhereArgs w;  // what the kernel receives
 };
 
-hipError_t launch_where_group_0(const WhereReq &);
-hipError_t launch_where_group_1(const WhereReq &);
-hipError_t launch_where_group_2(const WhereReq &);
-hipError_t launch_where_group_3(const WhereReq &);
-hipError_t launch_where_group_4(const WhereReq &);
-hipError_t launch_where_group_5(const WhereReq &);
-hipError_t launch_where_group_6(const WhereReq &);
-hipError_t launch_where_group_7(const WhereReq &);
+MI355_DECLARE_GROUPS(launch_where_group_, WhereReq);
 
 } // namespace mi355

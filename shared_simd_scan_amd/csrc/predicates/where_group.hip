@@ -1,8 +1,6 @@
 // where_group.hip -- instantiates the kernels of predicates/where.hpp for widths MI355_WLO..MI355_WHI and exports one
 // launcher per group.  Compiled 8 times (4 widths each), like width_group.hip.
-#include <atomic>
-#include <type_traits>
-
+#include "../launch_util.hpp"
 #include "where_dispatch.hpp"
 
 #ifndef MI355_WLO
@@ -14,24 +12,6 @@ namespace mi355 {
 namespace {
 
 constexpr int kWhereVpl = scan_vpl(0, kModeShared); // 64 values per lane and tile, as the equality shared scans
-
-template <typename K> int blocks_per_cu(K kernel)
-{
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlockThreads, 0) != hipSuccess || nb < 1) nb = 1;
-    return nb;
-}
-
-// dynamic LDS beyond the default 64 KiB: raised once per kernel and device
-template <auto Kernel> void allow_dynamic_lds(int max_bytes, int device)
-{
-    static std::atomic<unsigned long long> done{0};
-    const unsigned long long bit = 1ull << (device & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
-        done.fetch_or(bit, std::memory_order_release);
-    }
-}
 
 // ---- the fit rule ----------------------------------------------------------------------------
 // The multi-pass table kernel keeps ceil(P / 8) full tables of max(2^c, 4) bytes in dynamic LDS next to its static part:
@@ -65,75 +45,62 @@ template <int C> hipError_t launch_where(const WhereReq &r)
     const uint64_t ntiles = (s.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
     int choice = kWhereChain;
     if constexpr (C <= 16) choice = P <= 8 ? kWhereLut : (where_tables_fit<C>(P) ? kWhereLutMulti : kWhereChain);
-    if (r.l.choice_out) { // introspection (mi355_shared_where_kernel): nothing is launched
-        *r.l.choice_out = choice;
-        return hipSuccess;
-    }
+    if (r.l.choice_out) *r.l.choice_out = choice; // introspection (mi355_shared_where_kernel): MI355_LAUNCH launches nothing
     if constexpr (C <= 16) {
         if (choice == kWhereLut) {
             // result stores as shared_lut_kernel's launcher: write-through below 768 MiB of output, non-temporal beyond
-            const int spol = r.l.scan_nt_stores < 0 ? ((s.n / 8) * P > (768ull << 20) ? 1 : 2) : r.l.scan_nt_stores; // 0 plain, 1 nt, 2 sc1
+            const int spol = one_pass_store_policy((s.n / 8) * P, r.l.scan_nt_stores); // 0 plain, 1 nt, 2 sc1
             const size_t per_block = 4 * G::LDS_BYTES + WhereLutGeom<C>::TABLE_BYTES + (linear ? 4 * (VPL / 8) * 8 * 64 : 0) + 512;
             const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, per_block), r.l.num_cus));
             if (linear && spol == 1)
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 18, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 18, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
             else if (linear && spol == 2)
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 34, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 34, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
             else if (linear)
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 2, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
             else if (spol == 1)
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 18, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 18, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
             else if (spol == 2)
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 34, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 34, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
             else
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 2, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
-            return hipGetLastError();
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+            return launch_status(r.l);
         }
         if constexpr (where_tables_fit<C>(9)) // (c = 16: two tables never fit, the multi-pass form is not instantiated)
         if (choice == kWhereLutMulti) {
             // per-predicate result stores: non-temporal unless the P bitmaps together are small (the rule of the equality
             // scans of more than 8 keys)
-            const bool nt_stores = r.l.scan_nt_stores < 0 ? (s.n / 8) * P > (64ull << 20) : r.l.scan_nt_stores != 0;
+            const bool nt_stores = multi_pass_nt_stores((s.n / 8) * P, r.l.scan_nt_stores);
             const size_t dyn = where_table_bytes<C>(P);
             const int max_dyn = (int)(160 * 1024 - where_static_lds<C>());
             const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, dyn + where_static_lds<C>()), r.l.num_cus));
             if (linear) {
                 allow_dynamic_lds<shared_where_lut_kernel<C, 2, VPL, 1, true>>(max_dyn, r.l.device);
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 2, VPL, 1, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 1, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
             } else if (nt_stores) {
                 allow_dynamic_lds<shared_where_lut_kernel<C, 18, VPL, 0, true>>(max_dyn, r.l.device);
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 18, VPL, 0, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 18, VPL, 0, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
             } else {
                 allow_dynamic_lds<shared_where_lut_kernel<C, 2, VPL, 0, true>>(max_dyn, r.l.device);
-                MI355_LAUNCH(r.l.record, 0, (shared_where_lut_kernel<C, 2, VPL, 0, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
+                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 0, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
             }
-            return hipGetLastError();
+            return launch_status(r.l);
         }
     }
     if constexpr (C >= 11) { // (at c <= 10 every list fits the tables)
         static const int bpc = blocks_per_cu(shared_where_chain_kernel<C, 2, VPL>);
-        const int use = (r.l.max_blocks_per_cu > 0 && r.l.max_blocks_per_cu < bpc) ? r.l.max_blocks_per_cu : bpc;
-        MI355_LAUNCH(r.l.record, 0, (shared_where_chain_kernel<C, 2, VPL>), dim3(grid_for(ntiles, use, r.l.num_cus)), dim3(kBlockThreads), 0,
-                     r.l.stream, r.w);
-        return hipGetLastError();
+        MI355_LAUNCH(r.l, 0, (shared_where_chain_kernel<C, 2, VPL>), dim3(grid_for(ntiles, cap_bpc(bpc, r.l.max_blocks_per_cu), r.l.num_cus)),
+                     dim3(kBlockThreads), 0, r.l.stream, r.w);
+        return launch_status(r.l);
     }
     return hipErrorInvalidValue;
 }
 
-template <int C> hipError_t launch_where_from(const WhereReq &r)
-{
-    if (r.l.c == C) return launch_where<C>(r);
-    if constexpr (C < MI355_WHI)
-        return launch_where_from<C + 1>(r);
-    else
-        return hipErrorInvalidValue;
-}
-
 } // namespace
 
-#define MI355_CAT2(a, b) a##b
-#define MI355_CAT(a, b) MI355_CAT2(a, b)
-
-hipError_t MI355_CAT(launch_where_group_, MI355_GROUP)(const WhereReq &r) { return launch_where_from<MI355_WLO>(r); }
+hipError_t MI355_CAT(launch_where_group_, MI355_GROUP)(const WhereReq &r)
+{
+    return launch_by_width<MI355_WLO, MI355_WHI>(r.l.c, r, [](auto c, const WhereReq &q) { return launch_where<decltype(c)::value>(q); });
+}
 
 } // namespace mi355

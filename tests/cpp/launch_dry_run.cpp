@@ -1,0 +1,55 @@
+// launch_dry_run.cpp -- what the width-group launchers WOULD launch, without a GPU (tests/test_launch_plan.py).
+//
+// Links against csrc/build/width_group_*.o.  Every request carries LaunchReq::choice_out, so nothing is launched: the
+// launchers only decide, report the kernel family and write the launch-record line.  The occupancy queries have no device
+// to ask and fall back to one block per CU, so the grid column means nothing here.
+//
+// stdin, one case per line:  op c P layout hits n flags shared_vpl scan_nt_stores max_blocks_per_cu dma_aux scan_burst select_single
+// stdout, one line per case: <family or -1> TAB <launch record line>
+#include <cstdio>
+#include <string>
+
+#include "dispatch.hpp"
+
+using namespace mi355;
+
+int main()
+{
+    hipError_t (*const groups[kNumGroups])(const LaunchReq &) = MI355_GROUP_TABLE(launch_group_);
+    int op, layout, hits, shared_vpl, nts, max_bpc, dma_aux, burst, single;
+    unsigned c, P, flags;
+    unsigned long long n, dummy = 0;
+    while (scanf("%d %u %u %d %d %llu %u %d %d %d %d %d %d", &op, &c, &P, &layout, &hits, &n, &flags, &shared_vpl, &nts, &max_bpc, &dma_aux,
+                 &burst, &single) == 13) {
+        if (c < 1 || c > 32) return 2;
+        std::string record;
+        int family = -1;
+        LaunchReq r{};
+        r.op = op;
+        r.c = c;
+        r.num_cus = 256;
+        r.max_blocks_per_cu = max_bpc;
+        r.dma_aux = dma_aux;
+        r.scan_nt_stores = nts;
+        r.scan_burst = burst;
+        r.llc_resident_mib = -1;
+        r.select_single = single;
+        r.shared_vpl = shared_vpl;
+        r.record = &record;
+        r.choice_out = &family;
+        r.scan.n = n;
+        r.scan.nkeys = P;
+        r.scan.layout = (uint32_t)layout;
+        r.scan.hits = hits ? &dummy : nullptr;
+        r.scan.flags = flags;
+        r.decomp.n = n;
+        const hipError_t e = groups[(c - 1) / 4](r);
+        if (e != hipSuccess) {
+            fprintf(stderr, "op %d c %u P %u: %s\n", op, c, P, hipGetErrorString(e));
+            return 1;
+        }
+        if (!record.empty() && record.back() == '\n') record.pop_back();
+        printf("%d\t%s\n", family, record.c_str());
+    }
+    return 0;
+}

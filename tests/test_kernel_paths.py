@@ -5,7 +5,7 @@ CPU: every __global__ kernel of csrc/kernels/*.hpp and csrc/extras/*.hpp is the 
 axes the launcher picks between are covered; every kernel-side `flags & <const>` test maps (through the shifts in capi.hip)
 to an option bit of the matrix, and every option bit of the matrix has a case.
 GPU (-m gpu): each case runs, its launch record matches, and every output byte equals numpy, inside 0xEE guard bytes that
-must stay untouched.  A case with an option bit also runs without that bit: the record must change (the launcher really
+must stay untouched.  A shared scan also asks mi355_shared_scan_kernel under its options: the family named is the one launched.  A case with an option bit also runs without that bit: the record must change (the launcher really
 took the other path) and the results must not.  The counter-flush cases run on a 4-wave grid (grid_cus = 1,
 max_blocks_per_cu = 1) so that every wave walks more than 1100 tiles: the packed 16-bit hit counters flush at least twice.
 """
@@ -261,6 +261,17 @@ def base_name(label):
     return label.split("<", 1)[0]
 
 
+def family_of(label):
+    """the family mi355_shared_scan_kernel / mi355_shared_where_kernel names for the kernel of a launch-record label"""
+    name = base_name(label)
+    if name in ("shared_lut_kernel", "shared_where_lut_kernel") and label.split(">")[0].split(",")[-1].strip() == "true":
+        return name + "(multi-pass)"
+    for stem in ("shared_wide", "shared_linear"):
+        if name.startswith(stem):
+            return stem + "_kernel"
+    return name
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # CPU: the table covers every kernel, every variant axis and every option bit
 # ------------------------------------------------------------------------------------------------------------------------
@@ -319,9 +330,9 @@ def flag_shifts():
 
 
 def kernel_flag_tests():
-    """(file, kernel-side bit) for every `flags & <const>` of width_group.hip and kernels/*.hpp"""
+    """(file, kernel-side bit) for every `flags & <const>` of width_group.hip, shared_plan.hpp and kernels/*.hpp"""
     out = []
-    for f in [os.path.join(CSRC, "width_group.hip")] + sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hpp"))):
+    for f in [os.path.join(CSRC, "width_group.hip"), os.path.join(CSRC, "shared_plan.hpp")] + sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hpp"))):
         text = strip_comments(strip_debug_blocks(open(f).read()))
         for const in re.findall(r"\bflags\s*&\s*(0x[0-9a-fA-F]+|\d+)u?\b", text):
             v = int(const, 0)
@@ -498,9 +509,13 @@ class Runner:
         out = Guarded(P * stride if case.layout == 0 else P * nb)
         hits = Guarded(8 * P) if case.hits else None
         k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32).view(np.int32))
+        named = self.L.mi355_shared_scan_kernel(eng._ctx, c, P, case.layout, int(case.hits))  # under the case's options
         self.ok(self.L.mi355_shared_scan_eq_dev(eng._ctx, C.c_void_p(packed.data_ptr()), n, c, k.ctypes.data_as(C.c_void_p), P,
                                                 case.layout, out.ptr, stride, hits.ptr if hits else None))
         self.record(eng)
+        launched = parse_record(self.last_record)
+        assert len(launched) == 1 and named is not None and named.decode() == family_of(launched[0][0]), \
+            f"the library names {named}, launched:\n{self.last_record}"
         body = out.fetch()
         uniq = {}
         for key in keys:

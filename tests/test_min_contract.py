@@ -35,7 +35,7 @@ from dataclasses import dataclass
 import numpy as np
 import pytest
 
-from test_kernel_paths import SENTINEL, SHARED_TILE_ROWS, Guarded, base_name, packbits, parse_record
+from test_kernel_paths import SENTINEL, SHARED_TILE_ROWS, Guarded, base_name, family_of, packbits, parse_record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -614,16 +614,6 @@ class Runtime:
 
 def u64(g):
     return int(g.fetch().view(np.uint64)[0])
-
-
-def family_of(label):
-    name = base_name(label)
-    if name in ("shared_lut_kernel", "shared_where_lut_kernel") and label.split(">")[0].split(",")[-1].strip() == "true":
-        return name + "(multi-pass)"
-    for stem in ("shared_wide", "shared_linear"):
-        if name.startswith(stem):
-            return stem + "_kernel"
-    return name
 
 
 def run_case(rt, eng, case, model):

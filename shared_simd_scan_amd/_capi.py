@@ -1,4 +1,4 @@
-"""ctypes binding of include/mi355_scan.h and include/mi355_columns.h.  No compute happens in Python; a missing library is an error."""
+"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h and include/mi355_groupby.h.  No compute happens in Python; a missing library is an error."""
 from __future__ import annotations
 
 import ctypes as C
@@ -88,6 +88,11 @@ COLUMN_SYMBOLS = [
     ("mi355_scan_columns_dev", _int, [_vp, _vp, C.c_uint, _vp, C.c_uint, _u64, _int, C.c_int64, C.c_int64, _int, _vp, _vp, _vp]),
 ]
 
+# every symbol include/mi355_groupby.h declares (grouped aggregates over two columns): bound by lib() as well
+GROUP_SYMBOLS = [
+    ("mi355_group_aggregate_dev", _int, [_vp, _vp, C.c_uint, _vp, C.c_uint, _u64, _vp, _vp]),
+]
+
 
 class Predicate(C.Structure):
     """mi355_predicate: one comparison `v OP a [, b]` of a shared where-scan"""
@@ -107,7 +112,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the HIP extension is not built (run `python -m shared_simd_scan_amd.build`). "
                 "There is no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS + COLUMN_SYMBOLS:
+        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export what the header declares
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,92 @@
+// group_aggregate.hip -- implementation of include/mi355_groupby.h: argument checks and the launch of
+// group_aggregate_kernel (groupby/group_aggregate.hpp) by key width.  Its own translation unit: neither capi.hip nor the
+// width groups rebuild with it.
+#include "../ctx.hpp"
+
+#include <atomic>
+
+#include "../../../include/mi355_groupby.h"
+#include "../dispatch.hpp"
+#include "../launch_util.hpp"
+#include "group_aggregate.hpp"
+
+using namespace mi355;
+
+namespace {
+
+static_assert(kGroupMaxBits == MI355_GROUP_MAX_KEY_BITS, "the header's limit is the kernel's");
+
+struct GroupLaunch {
+    GroupArgs k;
+    unsigned ck;
+    hipStream_t stream;
+    int device, num_cus, max_blocks_per_cu;
+    std::string *record;
+};
+
+template <int CK> hipError_t launch_group(const GroupLaunch &r)
+{
+    using G = ScanGeom<CK, kGroupVpl>;
+    const uint32_t cv = r.k.cv;
+    const uint64_t ntiles = (r.k.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
+    const size_t lds = group_block_lds<CK>(cv);
+    allow_dynamic_lds<group_aggregate_kernel<CK>>((int)group_block_lds<CK>(32), r.device);
+    // Blocks per CU: small tiles, LDS reads and atomics all through a tile -- as many blocks as LDS and registers admit, up to
+    // 4 waves per SIMD (the rule of scan_columns_kernel's run-time-width form).  The query depends on the dynamic LDS, i.e.
+    // on cv: asked once per value width.
+    static std::atomic<int> bpc_of[33];
+    int bpc = bpc_of[cv].load(std::memory_order_relaxed);
+    if (bpc == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, group_aggregate_kernel<CK>, kBlockThreads, lds) != hipSuccess || bpc < 1) bpc = 1;
+        if (bpc > 4) bpc = 4;
+        bpc_of[cv].store(bpc, std::memory_order_relaxed);
+    }
+    unsigned grid = grid_for(ntiles, cap_bpc(bpc, r.max_blocks_per_cu), r.num_cus);
+    // a block's counts are 32-bit words in LDS: no block may see 2^32 rows (a grid beyond what is resident simply queues)
+    const uint64_t min_grid = (r.k.n >> 31) + 1;
+    if (grid < min_grid) grid = (unsigned)min_grid;
+    MI355_LAUNCH(r.record, 0, group_aggregate_init_kernel, dim3(((1u << CK) + 255u) / 256u), dim3(256), 0, r.stream, r.k.out, 1u << CK);
+    MI355_LAUNCH(r.record, 0, (group_aggregate_kernel<CK>), dim3(grid), dim3(kBlockThreads), lds, r.stream, r.k);
+    return hipGetLastError();
+}
+
+} // namespace
+
+int mi355_group_aggregate_dev(mi355_ctx *ctx, const void *keys_dev, unsigned ck, const void *values_dev, unsigned cv, uint64_t n,
+                              const void *mask_dev, uint64_t *out_dev)
+{
+    int rc = resolve(ctx);
+    if (rc) return rc;
+    CtxLock lk(ctx->mu);
+    CallScope cs(ctx);
+    if (ck < 1 || ck > (unsigned)kGroupMaxBits)
+        return fail(MI355_E_INVALID, "group_aggregate: key widths 1..%d bits (the groups' state lives in LDS), got ck=%u", kGroupMaxBits, ck);
+    if (cv < 1 || cv > 32) return fail(MI355_E_INVALID, "group_aggregate: value width cv=%u outside 1..32", cv);
+    if (!out_dev) return fail(MI355_E_INVALID, "group_aggregate: out_dev is null");
+    if (n && !keys_dev) return fail(MI355_E_INVALID, "group_aggregate: keys_dev is null");
+    if (n && !values_dev) return fail(MI355_E_INVALID, "group_aggregate: values_dev is null (count(*) per value of one column: mi355_histogram_dev)");
+    if (((uintptr_t)keys_dev & 15) || ((uintptr_t)values_dev & 15) || ((uintptr_t)mask_dev & 3) || ((uintptr_t)out_dev & 7))
+        return fail(MI355_E_INVALID, "group_aggregate: keys_dev / values_dev must be 16-byte, mask_dev 4-byte, out_dev 8-byte aligned");
+    if ((rc = bind(ctx))) return rc;
+    GroupLaunch r{};
+    r.k.keys = (const uint8_t *)keys_dev;
+    r.k.values = (const uint8_t *)values_dev;
+    r.k.n = n;
+    r.k.mask = (const uint8_t *)mask_dev;
+    r.k.out = (unsigned long long *)out_dev;
+    r.k.cv = cv;
+    r.ck = ck;
+    r.stream = ctx->stream;
+    r.device = ctx->device;
+    r.num_cus = grid_cus(ctx);
+    r.max_blocks_per_cu = ctx->max_blocks_per_cu;
+    r.record = &ctx->last_launch;
+    if (n == 0) {
+        MI355_LAUNCH(r.record, 0, group_aggregate_init_kernel, dim3(((1u << ck) + 255u) / 256u), dim3(256), 0, r.stream, r.k.out, 1u << ck);
+        HIP_TRY(hipGetLastError());
+        return MI355_OK;
+    }
+    const hipError_t e = launch_by_width<1, kGroupMaxBits>(ck, r, [](auto c, const GroupLaunch &q) { return launch_group<decltype(c)::value>(q); });
+    if (e != hipSuccess) return fail(MI355_E_HIP, "group_aggregate launch: %s", hipGetErrorString(e));
+    return MI355_OK;
+}

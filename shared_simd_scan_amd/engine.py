@@ -389,6 +389,20 @@ class ScanEngine:
                                         out.data_ptr()))
         return out
 
+    def group_aggregate(self, keys: PackedColumn, values: PackedColumn, mask: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> int64[2^keys.c, 4] device tensor: row g = (sum, count, min, max) of `values` over the rows whose key is g, among
+        the rows of `mask` (a result bitmap; None = every row) -- SELECT g, sum(v), count(*), min(v), max(v) ... GROUP BY g in
+        one pass over both packed columns.  keys.c <= 12; a group without rows reads (0, 0, -1, 0) like aggregate()."""
+        assert keys.n == values.n
+        groups = 1 << keys.c
+        if out is None:
+            out = torch.empty((groups, 4), dtype=torch.int64, device=self._dev)
+        assert tuple(out.shape) == (groups, 4) and out.dtype == torch.int64 and out.is_contiguous()
+        check(lib().mi355_group_aggregate_dev(self._ctx, keys.data.data_ptr(), keys.c, values.data.data_ptr(), values.c, keys.n,
+                                              mask.data_ptr() if mask is not None else None, out.data_ptr()))
+        return out
+
     # ---- shared scans (src/simd_scan_shared.cpp, src/simd_scan_shared_linear.cpp) -----------------
     def shared_scan(self, keys: Sequence[int], col: PackedColumn, layout: str = "per_predicate",
                     out: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):

@@ -10,6 +10,7 @@
 // RCCL is bound at run time (dlopen): a host that never shards needs no librccl, and inside a PyTorch process the
 // already-loaded librccl is the one that is used.
 #include "ctx.hpp"
+#include "checks.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -109,7 +110,7 @@ extern "C" {
 
 int mi355_comm_get_unique_id(void *id_out)
 {
-    if (!id_out) return fail(MI355_E_INVALID, "id_out is null");
+    MI355_CHECK(check_ptr(id_out, "id_out"));
     Rccl *R = rccl();
     if (!R->handle) return fail(MI355_E_COMM, "%s", R->why.c_str());
     ncclUniqueId id;
@@ -120,14 +121,14 @@ int mi355_comm_get_unique_id(void *id_out)
 
 int mi355_comm_create(mi355_ctx *ctx, int world, int rank, const void *id, mi355_comm **out)
 {
-    int rc = resolve(ctx);
-    if (rc) return rc;
-    if (!out || !id) return fail(MI355_E_INVALID, "null pointer");
+    Locked lk(ctx);
+    if (lk.rc) return lk.rc;
+    MI355_CHECK(check_ptr(out, "out"));
+    MI355_CHECK(check_ptr(id, "id"));
     if (world < 1 || rank < 0 || rank >= world) return fail(MI355_E_INVALID, "rank %d outside a world of %d", rank, world);
     Rccl *R = rccl();
     if (!R->handle) return fail(MI355_E_COMM, "%s", R->why.c_str());
-    CtxLock lk(ctx->mu);
-    if ((rc = bind(ctx))) return rc; // ncclCommInitRank binds the communicator to the current device
+    MI355_CHECK(bind(ctx)); // ncclCommInitRank binds the communicator to the current device
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);
     mi355_comm *c = new mi355_comm;
@@ -164,13 +165,13 @@ int mi355_comm_info(const mi355_comm *comm, int *world, int *rank)
 int mi355_gather_bitmaps_at_dev(mi355_ctx *ctx, mi355_comm *comm, const void *local_dev, const uint64_t *bytes_per_rank,
                                 const uint64_t *offset_per_rank, int root, void *out_dev)
 {
-    int rc = resolve(ctx);
-    if (rc) return rc;
-    if (!comm || !bytes_per_rank) return fail(MI355_E_INVALID, "null pointer");
+    MI355_ENTER(ctx);
+    MI355_CHECK(check_ptr(comm, "comm"));
+    MI355_CHECK(check_ptr(bytes_per_rank, "bytes_per_rank"));
     if (root < 0 || root >= comm->world) return fail(MI355_E_INVALID, "root %d outside a world of %d", root, comm->world);
     if (ctx->device != comm->device) return fail(MI355_E_INVALID, "context and communicator are bound to different devices");
     const uint64_t mine = bytes_per_rank[comm->rank];
-    if (mine && !local_dev) return fail(MI355_E_INVALID, "local_dev is null");
+    if (mine) MI355_CHECK(check_ptr(local_dev, "local_dev"));
     uint64_t total = 0;
     for (int r = 0; r < comm->world; r++) total += bytes_per_rank[r];
     if (comm->rank == root && total && !out_dev) return fail(MI355_E_INVALID, "out_dev is null on the root");
@@ -189,9 +190,6 @@ int mi355_gather_bitmaps_at_dev(mi355_ctx *ctx, mi355_comm *comm, const void *lo
     }
     Rccl *R = rccl();
     if (!R->handle) return fail(MI355_E_COMM, "%s", R->why.c_str());
-    CtxLock lk(ctx->mu);
-    CallScope cs(ctx);
-    if ((rc = bind(ctx))) return rc;
     if (comm->rank != root) {
         if (mine) RCCL_TRY(R, R->Send(local_dev, (size_t)mine, ncclUint8, root, comm->comm, ctx->stream));
         return MI355_OK;
@@ -230,15 +228,12 @@ int mi355_gather_bitmaps_dev(mi355_ctx *ctx, mi355_comm *comm, const void *local
 
 int mi355_allreduce_hits_dev(mi355_ctx *ctx, mi355_comm *comm, uint64_t *hits_dev, unsigned count)
 {
-    int rc = resolve(ctx);
-    if (rc) return rc;
-    if (!comm || !hits_dev) return fail(MI355_E_INVALID, "null pointer");
+    MI355_ENTER(ctx);
+    MI355_CHECK(check_ptr(comm, "comm"));
+    MI355_CHECK(check_ptr(hits_dev, "hits_dev"));
     if (ctx->device != comm->device) return fail(MI355_E_INVALID, "context and communicator are bound to different devices");
     if (count == 0) return MI355_OK;
     Rccl *R = rccl();
-    CtxLock lk(ctx->mu);
-    CallScope cs(ctx);
-    if ((rc = bind(ctx))) return rc;
     RCCL_TRY(R, R->AllReduce(hits_dev, hits_dev, count, ncclUint64, ncclSum, comm->comm, ctx->stream));
     return MI355_OK;
 }
@@ -246,7 +241,6 @@ int mi355_allreduce_hits_dev(mi355_ctx *ctx, mi355_comm *comm, uint64_t *hits_de
 static int sharded_finish(mi355_ctx *ctx, mi355_comm *comm, const void *local_bitmap_dev, const uint64_t *rows_per_rank,
                           int root, void *full_bitmap_dev, uint64_t *hits_dev)
 {
-    if (!rows_per_rank) return fail(MI355_E_INVALID, "rows_per_rank is null");
     std::vector<uint64_t> bytes(comm->world);
     for (int r = 0; r < comm->world; r++) {
         // every shard but the last must end on a whole bitmap byte, or the slices could not be laid end to end
@@ -255,22 +249,18 @@ static int sharded_finish(mi355_ctx *ctx, mi355_comm *comm, const void *local_bi
                                          "(mi355_shard_rows yields multiples of 8192)", r, (unsigned long long)rows_per_rank[r]);
         bytes[r] = (rows_per_rank[r] + 7) / 8;
     }
-    int rc = mi355_gather_bitmaps_dev(ctx, comm, local_bitmap_dev, bytes.data(), root, full_bitmap_dev);
-    if (rc) return rc;
-    if (hits_dev) rc = mi355_allreduce_hits_dev(ctx, comm, hits_dev, 1);
-    return rc;
+    MI355_CHECK(mi355_gather_bitmaps_dev(ctx, comm, local_bitmap_dev, bytes.data(), root, full_bitmap_dev));
+    return hits_dev ? mi355_allreduce_hits_dev(ctx, comm, hits_dev, 1) : MI355_OK;
 }
 
 int mi355_sharded_scan_eq_dev(mi355_ctx *ctx, mi355_comm *comm, const void *packed_dev, unsigned c, int32_t key,
                               void *local_bitmap_dev, const uint64_t *rows_per_rank, int root, void *full_bitmap_dev,
                               uint64_t *hits_dev)
 {
-    int rc = resolve(ctx);
-    if (rc) return rc;
-    if (!comm || !rows_per_rank) return fail(MI355_E_INVALID, "null pointer");
-    CtxLock lk(ctx->mu);
-    CallScope cs(ctx);
-    if ((rc = mi355_scan_eq_dev(ctx, packed_dev, rows_per_rank[comm->rank], c, key, local_bitmap_dev, hits_dev))) return rc;
+    MI355_ENTER(ctx);
+    MI355_CHECK(check_ptr(comm, "comm"));
+    MI355_CHECK(check_ptr(rows_per_rank, "rows_per_rank"));
+    MI355_CHECK(mi355_scan_eq_dev(ctx, packed_dev, rows_per_rank[comm->rank], c, key, local_bitmap_dev, hits_dev));
     return sharded_finish(ctx, comm, local_bitmap_dev, rows_per_rank, root, full_bitmap_dev, hits_dev);
 }
 
@@ -278,12 +268,10 @@ int mi355_sharded_scan_range_dev(mi355_ctx *ctx, mi355_comm *comm, const void *p
                                  uint32_t hi, void *local_bitmap_dev, const uint64_t *rows_per_rank, int root,
                                  void *full_bitmap_dev, uint64_t *hits_dev)
 {
-    int rc = resolve(ctx);
-    if (rc) return rc;
-    if (!comm || !rows_per_rank) return fail(MI355_E_INVALID, "null pointer");
-    CtxLock lk(ctx->mu);
-    CallScope cs(ctx);
-    if ((rc = mi355_scan_range_dev(ctx, packed_dev, rows_per_rank[comm->rank], c, lo, hi, local_bitmap_dev, hits_dev))) return rc;
+    MI355_ENTER(ctx);
+    MI355_CHECK(check_ptr(comm, "comm"));
+    MI355_CHECK(check_ptr(rows_per_rank, "rows_per_rank"));
+    MI355_CHECK(mi355_scan_range_dev(ctx, packed_dev, rows_per_rank[comm->rank], c, lo, hi, local_bitmap_dev, hits_dev));
     return sharded_finish(ctx, comm, local_bitmap_dev, rows_per_rank, root, full_bitmap_dev, hits_dev);
 }
 

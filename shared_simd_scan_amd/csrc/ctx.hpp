@@ -1,5 +1,6 @@
-// ctx.hpp -- the context object behind include/mi355_scan.h and the helpers every host-side translation unit of
-// libmi355scan.so shares (capi.hip, comm.hip): error reporting, default-context resolution, locking.
+// ctx.hpp -- the context object behind include/mi355_scan.h and what every host-side translation unit of libmi355scan.so
+// shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip, groupby/group_aggregate.hip):
+// error reporting, the entry prologue, the context's buffers.
 #pragma once
 
 #include "../../include/mi355_scan.h"
@@ -12,6 +13,10 @@
 #include <mutex>
 #include <string>
 #include <vector>
+
+namespace mi355 {
+constexpr int kKeySlots = 8; // slots of the upload ring (context.hip upload_list)
+}
 
 struct mi355_ctx {
     int device = 0;
@@ -48,8 +53,8 @@ struct mi355_ctx {
     // kKeySlots calls ago)
     int32_t *keys_scratch = nullptr;            // device: kKeySlots x 3 x (1024 + 8) dwords
     int32_t *keys_pinned = nullptr;             // host (pinned): the same
-    hipEvent_t key_events[8] = {};
-    bool key_used[8] = {};
+    hipEvent_t key_events[mi355::kKeySlots] = {};
+    bool key_used[mi355::kKeySlots] = {};
     int key_next = 0;
     hipEvent_t order_event = nullptr;           // mi355_ctx_set_stream: new stream waits for the old one
     unsigned long long *rowid_ws = nullptr;     // chunk counts of mi355_bitmap_to_rowids_dev / mi355_scan_select_dev
@@ -82,27 +87,70 @@ const char *last_error();
         if (e_ != hipSuccess) return ::mi355::fail(MI355_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// ctx == NULL -> the calling thread's default context (device 0, the null stream), created on first use and
-// destroyed when the thread exits
-int resolve(mi355_ctx *&ctx);
-// a context is bound to one device: make it current for this thread before touching it
+// a context is bound to one device: make it current for this thread before touching it.  Called by the prologue below, and
+// by the two calls that need the device current without being a compute call (mi355_ctx_set_stream, mi355_comm_create).
 int bind(mi355_ctx *ctx);
-// grow-only device buffer of the context (host-pointer flavours); the caller holds ctx->mu
-int pool_get(mi355_ctx *ctx, int slot, size_t bytes, void **out);
+// ctx == NULL -> the calling thread's default context (device 0, the null stream), created on first use and destroyed when
+// the thread exits.  Only the prologue calls it.
+int resolve(mi355_ctx *&ctx);
 
-typedef std::lock_guard<std::recursive_mutex> CtxLock;
-
-// a compute entry point in progress, taken after the context's lock: the outermost one starts a new launch record
-struct CallScope {
-    mi355_ctx *ctx;
-    explicit CallScope(mi355_ctx *c) : ctx(c)
+// ---- the prologue of every entry point that takes a context ----
+// Locked: resolves the default context and holds the context's lock.  On its own it is the prologue of the accessors, which
+// neither touch the device nor start a launch record.
+struct Locked {
+    int rc;
+    mi355_ctx *ctx = nullptr;
+    explicit Locked(mi355_ctx *&c) : rc(resolve(c))
     {
-        if (ctx->call_depth++ == 0) ctx->last_launch.clear();
+        if (rc) return;
+        ctx = c;
+        ctx->mu.lock();
     }
-    ~CallScope() { ctx->call_depth--; }
-    CallScope(const CallScope &) = delete;
-    CallScope &operator=(const CallScope &) = delete;
+    ~Locked() { if (ctx) ctx->mu.unlock(); }
+    Locked(const Locked &) = delete;
+    Locked &operator=(const Locked &) = delete;
 };
+
+// Entry, through MI355_ENTER(ctx) as an entry point's first line: Locked, then the outermost call on this context (the
+// host-pointer flavours, the compound calls and the sharded scans call other entry points with the lock held) starts a new launch
+// record and makes the context's device current.  Nested calls bind nothing: the outermost one did.  kKeepRecord: the memory
+// helpers and mi355_ctx_synchronize, which queue work on the context's stream but launch nothing -- the record of the last
+// compute call stays readable behind them.
+struct Entry : Locked {
+    enum Record { kNewRecord, kKeepRecord };
+    explicit Entry(mi355_ctx *&c, Record record = kNewRecord) : Locked(c), counted(!rc && record == kNewRecord)
+    {
+        if (rc) return;
+        const bool outermost = ctx->call_depth == 0;
+        if (counted) ctx->call_depth++;
+        if (!outermost) return;
+        if (counted) ctx->last_launch.clear();
+        rc = bind(ctx);
+    }
+    ~Entry() { if (counted) ctx->call_depth--; }
+    const bool counted;
+};
+#define MI355_ENTER(...)                \
+    ::mi355::Entry entry_(__VA_ARGS__); \
+    if (entry_.rc) return entry_.rc
+
+// Is `stream` being captured into a graph?  The one capture check of the library.  kCaptureUnknown: the runtime would not say
+// (e.g. the null stream while another stream captures in global mode); whoever is about to synchronise, allocate, free or copy
+// from host memory treats that as kCaptureOn and refuses -- being wrong the other way invalidates somebody's capture.
+// *id (nullable) gets the capture's id, 0 unless kCaptureOn.
+enum CaptureState { kCaptureOff = 0, kCaptureOn = 1, kCaptureUnknown = 2 };
+CaptureState capture_state(hipStream_t stream, unsigned long long *id = nullptr);
+inline CaptureState capture_state(mi355_ctx *ctx, unsigned long long *id = nullptr) { return capture_state(ctx->stream, id); }
+
+// ---- the context's buffers (context.hip); the caller holds ctx->mu ----
+// grow-only device buffer of the context (host-pointer flavours, temporaries of compound calls)
+int pool_get(mi355_ctx *ctx, int slot, size_t bytes, void **out);
+// the selection workspace holds at least `entries` words (grown outside capture only; kept alive once a graph points at it)
+int rowid_ws_get(mi355_ctx *ctx, uint64_t entries, const char *what);
+// A list of P elements of elem_bytes (at most 12: a key, or a (lo, span, negate) triple; P <= kMaxKeys) -> device memory,
+// padded to a multiple of 8 elements with copies of the last, asynchronously on the stream, through the ring of kKeySlots
+// pinned / device slots.  `what`: the refusal under capture.
+int upload_list(mi355_ctx *ctx, const void *src, size_t elem_bytes, unsigned P, const char *what, const void **dev);
 
 // CUs the persistent grids are sized for (option "grid_cus")
 inline int grid_cus(const mi355_ctx *ctx) { return ctx->grid_cus > 0 ? ctx->grid_cus : ctx->num_cus; }

@@ -1,7 +1,7 @@
 // extras/aggregate.hpp -- sum / min / max / count of a packed column, optionally only over the rows of a bitmap
 // (SELECT sum(b), min(b), max(b), count(*) WHERE <bitmap>): the consumer that ends most predicate chains.  Built from the
 // scan's pipeline (kernels/tile.hpp, kernels/scan.hpp: LDS-DMA tiles, lane owns a run, compile-time bit offsets) but not
-// one of the profiled hot-path kernels; included by capi.hip only.
+// one of the profiled hot-path kernels; included by extras.hip only.
 #pragma once
 
 #include "../dispatch.hpp"

@@ -1,6 +1,6 @@
 // extras/gather.hpp -- values of a packed column at given row ids (the step after a selection vector: "take").
 // Not one of the profiled hot-path kernels (kernels/*.hpp): a consumer either side of the scan, included by
-// capi.hip only.
+// extras.hip only.
 #pragma once
 
 #include <hip/hip_runtime.h>

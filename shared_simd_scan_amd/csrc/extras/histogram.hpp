@@ -1,7 +1,7 @@
 // extras/histogram.hpp -- how often every value occurs in a packed column (SELECT v, count(*) ... GROUP BY v -- with the
 // c-bit value a dictionary index, the usual aggregation over a dictionary-coded column), optionally only over the rows of a
 // bitmap.  Widths up to 14 bits: the 2^c counters live in LDS, one LDS atomic per value, one global atomic per non-empty
-// counter and block at the end.  Built from the scan's tile pipeline; included by capi.hip only.
+// counter and block at the end.  Built from the scan's tile pipeline; included by extras.hip only.
 #pragma once
 
 #include "../dispatch.hpp"

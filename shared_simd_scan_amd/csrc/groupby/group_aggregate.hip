@@ -1,11 +1,12 @@
 // group_aggregate.hip -- implementation of include/mi355_groupby.h: argument checks and the launch of
-// group_aggregate_kernel (groupby/group_aggregate.hpp) by key width.  Its own translation unit: neither capi.hip nor the
+// group_aggregate_kernel (groupby/group_aggregate.hpp) by key width.  Its own translation unit: neither the other entry points nor the
 // width groups rebuild with it.
 #include "../ctx.hpp"
 
 #include <atomic>
 
 #include "../../../include/mi355_groupby.h"
+#include "../checks.hpp"
 #include "../dispatch.hpp"
 #include "../launch_util.hpp"
 #include "group_aggregate.hpp"
@@ -55,19 +56,15 @@ template <int CK> hipError_t launch_group(const GroupLaunch &r)
 int mi355_group_aggregate_dev(mi355_ctx *ctx, const void *keys_dev, unsigned ck, const void *values_dev, unsigned cv, uint64_t n,
                               const void *mask_dev, uint64_t *out_dev)
 {
-    int rc = resolve(ctx);
-    if (rc) return rc;
-    CtxLock lk(ctx->mu);
-    CallScope cs(ctx);
-    if (ck < 1 || ck > (unsigned)kGroupMaxBits)
-        return fail(MI355_E_INVALID, "group_aggregate: key widths 1..%d bits (the groups' state lives in LDS), got ck=%u", kGroupMaxBits, ck);
-    if (cv < 1 || cv > 32) return fail(MI355_E_INVALID, "group_aggregate: value width cv=%u outside 1..32", cv);
-    if (!out_dev) return fail(MI355_E_INVALID, "group_aggregate: out_dev is null");
-    if (n && !keys_dev) return fail(MI355_E_INVALID, "group_aggregate: keys_dev is null");
-    if (n && !values_dev) return fail(MI355_E_INVALID, "group_aggregate: values_dev is null (count(*) per value of one column: mi355_histogram_dev)");
-    if (((uintptr_t)keys_dev & 15) || ((uintptr_t)values_dev & 15) || ((uintptr_t)mask_dev & 3) || ((uintptr_t)out_dev & 7))
-        return fail(MI355_E_INVALID, "group_aggregate: keys_dev / values_dev must be 16-byte, mask_dev 4-byte, out_dev 8-byte aligned");
-    if ((rc = bind(ctx))) return rc;
+    MI355_ENTER(ctx);
+    MI355_CHECK(check_width(ck, "ck", kGroupMaxBits, " (group_aggregate: the groups' state lives in LDS)"));
+    MI355_CHECK(check_width(cv, "cv"));
+    MI355_CHECK(check_dev(out_dev, 8, "out_dev"));
+    if (n) MI355_CHECK(check_ptr(keys_dev, "keys_dev"));
+    if (n && !values_dev) return fail(MI355_E_INVALID, "pointer values_dev is null (count(*) per value of one column: mi355_histogram_dev)");
+    MI355_CHECK(check_aligned(keys_dev, 16, "keys_dev"));
+    MI355_CHECK(check_aligned(values_dev, 16, "values_dev"));
+    MI355_CHECK(check_aligned(mask_dev, 4, "mask_dev"));
     GroupLaunch r{};
     r.k.keys = (const uint8_t *)keys_dev;
     r.k.values = (const uint8_t *)values_dev;
@@ -86,7 +83,7 @@ int mi355_group_aggregate_dev(mi355_ctx *ctx, const void *keys_dev, unsigned ck,
         HIP_TRY(hipGetLastError());
         return MI355_OK;
     }
-    const hipError_t e = launch_by_width<1, kGroupMaxBits>(ck, r, [](auto c, const GroupLaunch &q) { return launch_group<decltype(c)::value>(q); });
-    if (e != hipSuccess) return fail(MI355_E_HIP, "group_aggregate launch: %s", hipGetErrorString(e));
+    const hipError_t err = launch_by_width<1, kGroupMaxBits>(ck, r, [](auto c, const GroupLaunch &q) { return launch_group<decltype(c)::value>(q); });
+    if (err != hipSuccess) return fail(MI355_E_HIP, "group_aggregate launch: %s", hipGetErrorString(err));
     return MI355_OK;
 }

@@ -54,7 +54,7 @@ AND, OR, XOR, ANDNOT = range(4)
 OP_NAMES = ("eq", "ne", "lt", "le", "gt", "ge", "between", "notbetween")
 MASK_NAMES = ("and", "or", "xor", "andnot")
 
-# the pointers capi.hip accepts at 4 bytes; every other device pointer below needs 16
+# the pointers extras.hip accepts at 4 bytes; every other device pointer below needs 16
 MIN_ALIGN_4 = {("mi355_bitmap_to_rowids_dev", "bitmap_dev"), ("mi355_gather_dev", "packed_dev"), ("mi355_aggregate_dev", "mask_dev"),
                ("mi355_histogram_dev", "mask_dev"), ("mi355_pack_u32_dev", "packed_dev"), ("mi355_pack_u16_dev", "packed_dev"),
                ("mi355_generate_dev", "packed_dev")}

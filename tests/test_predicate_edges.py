@@ -286,7 +286,7 @@ def test_predicate_constants_at_type_limits(O, eng, L, c):
         for layout in ("per_predicate", "linear"):
             out, hs = eng.shared_scan(ks, col, layout=layout)
             shared.append((P, layout, ks, out, hs))
-    # the int64 limits straight into the C ABI: the Python wrappers clamp them, so only here do they reach fill_predicate
+    # the int64 limits straight into the C ABI: the Python wrappers clamp them, so only here do they reach normalise_predicate
     ptr, ctx = col.data.data_ptr(), eng._ctx
     for op in CMP:
         for a in (INT64_MIN, INT64_MAX):

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(kBlockThreads) void decompress_kernel(DecompArgs a)
 {
     using G = DecompGeom<C>;
     constexpr int AUX = AUX_ & 15;          // cache policy of the DMA loads
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // stores of the int32 output: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // stores of the int32 output: 1 non-temporal, 2 write-through (sc1)
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

@@ -16,7 +16,7 @@ __global__ __launch_bounds__(kBlockThreads) void in_kernel(ScanArgs a)
     using G = ScanGeom<C, VPL>;
     constexpr int WORDS = G::WORDS;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // bitmap stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // bitmap stores: 1 non-temporal, 2 write-through (sc1)
     constexpr bool BITSET = C <= 16;
     constexpr int SET_BYTES = BITSET ? ((1 << (C < 16 ? C : 16)) + 7) / 8 : 16;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];

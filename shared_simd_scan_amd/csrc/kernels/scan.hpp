@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kBlockThreads, (burst_occ<C, VPL, K>())) void scan_
     static_assert(MODE == kModeEq || MODE == kModeRange, "MODE");
     constexpr int WORDS = G::WORDS;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0);
+    constexpr int NTS = store_policy_of(AUX_);
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     constexpr int LK = narrow_k<C>(); // values per table lookup (0: compare chain)
     __shared__ __attribute__((aligned(16))) uint8_t nlut[LK ? (1 << (LK * C)) : 16];
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(kBlockThreads, (burst_occ<C, VPL, 1>() > 1 ? burst_
     using G = ScanGeom<C, VPL>;
     constexpr int WORDS = G::WORDS;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0);
+    constexpr int NTS = store_policy_of(AUX_);
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][2][G::LDS_BYTES];
 
     const int lane = threadIdx.x & 63;

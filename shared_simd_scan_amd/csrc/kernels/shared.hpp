@@ -17,7 +17,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_general_kernel(ScanArgs 
     constexpr int AUX = AUX_ & 15;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     __shared__ uint32_t s_hits[kMaxKeys];
-    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    block_hits_clear(s_hits);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_pair_kernel(ScanArgs a)
     using G = ScanGeom<C, VPL>;
     constexpr int WORDS = G::WORDS;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // result stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // result stores: 1 non-temporal, 2 write-through (sc1)
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -417,15 +417,14 @@ __global__ __launch_bounds__(kBlockThreads) void shared_lut_kernel(ScanArgs a)
     constexpr int WORDS = G::WORDS;
     constexpr int GROUPS = VPL / 8;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // result stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // result stores: 1 non-temporal, 2 write-through (sc1)
     constexpr int NRES = LAYOUT == 0 ? 8 * WORDS : GROUPS * 2; // result dwords per lane, tile and pass
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     __shared__ __attribute__((aligned(16))) uint8_t lut_static[(MULTI || L::TABLE_BYTES < 16) ? 16 : L::TABLE_BYTES];
     uint8_t *const lut = MULTI ? mi355_dyn_lds : lut_static; // MULTI: npass * TABLE_BYTES dynamic bytes
     __shared__ uint32_t s_hits[MULTI ? kMaxKeys : 1];          // MULTI: per-block hit counters (block_hits_add8)
     __shared__ __attribute__((aligned(16))) uint8_t stage[(LAYOUT == 1 && !MULTI) ? kWavesPerBlock : 1][(LAYOUT == 1 && !MULTI) ? GROUPS * 8 * 64 : 16];
-    if constexpr (MULTI)
-        for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    if constexpr (MULTI) block_hits_clear(s_hits);
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -814,11 +813,11 @@ __global__ __launch_bounds__(kBlockThreads) void shared_wide_kernel(ScanArgs a)
     constexpr int WORDS = G::WORDS;
     constexpr int GROUPS = VPL / 8;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // result stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // result stores: 1 non-temporal, 2 write-through (sc1)
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     __shared__ uint32_t s_hits[kMaxKeys]; // per-block hit counters (block_hits_add8)
     uint32_t *const lut = (uint32_t *)mi355_dyn_lds; // ceil(P/32) * TABLE_BYTES dynamic bytes
-    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    block_hits_clear(s_hits);
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1009,7 +1008,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_wide2_kernel(ScanArgs a)
     constexpr bool REGCNT = RC == 1;
     constexpr int WORDS = G::WORDS;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // result stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // result stores: 1 non-temporal, 2 write-through (sc1)
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     __shared__ uint32_t s_hits[kMaxKeys]; // per-block hit counters (block_hits_add8)
     // Hit counts by HISTOGRAM while 2^C counters fit in LDS: hits[k] = number of values equal to keys[k], whatever P is --
@@ -1021,7 +1020,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_wide2_kernel(ScanArgs a)
     constexpr bool HIST = C <= 12;
     __shared__ uint32_t hist[HIST ? (1 << C) : 1];
     uint32_t *const lut = (uint32_t *)mi355_dyn_lds; // ceil(P/32) * TABLE_BYTES dynamic bytes
-    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    block_hits_clear(s_hits);
     if constexpr (HIST)
         for (uint32_t k = threadIdx.x; k < (1u << C); k += kBlockThreads) hist[k] = 0;
 
@@ -1321,7 +1320,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_linear_kernel(ScanArgs a
     constexpr bool HIST = C <= 12; // hit counts by histogram of the values (see shared_wide2_kernel), else packed byte counters
     __shared__ uint32_t hist[HIST ? (1 << C) : 1];
     uint32_t *const lut = (uint32_t *)mi355_dyn_lds; // ceil(P/32) tables of TABLE_BYTES
-    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    block_hits_clear(s_hits);
     if constexpr (HIST)
         for (uint32_t k = threadIdx.x; k < (1u << C); k += kBlockThreads) hist[k] = 0;
 
@@ -1627,7 +1626,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_linear2_kernel(ScanArgs 
     constexpr bool HIST = C <= 12; // hit counts by histogram of the values (see shared_wide2_kernel), else packed byte counters
     __shared__ uint32_t hist[HIST ? (1 << C) : 1];
     uint32_t *const lut = (uint32_t *)mi355_dyn_lds; // ceil(P/32) tables of TABLE_BYTES
-    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    block_hits_clear(s_hits);
     if constexpr (HIST)
         for (uint32_t k = threadIdx.x; k < (1u << C); k += kBlockThreads) hist[k] = 0;
 
@@ -1894,7 +1893,7 @@ __global__ __launch_bounds__(kBlockThreads, ((RC == 0 || C <= 10) ? 3 : 2)) void
     using L = WideLutGeom<C, BIG>;
     constexpr int WORDS = G::WORDS;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // result stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // result stores: 1 non-temporal, 2 write-through (sc1)
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     uint32_t *const lut = (uint32_t *)mi355_dyn_lds; // ceil(P/32) * TABLE_BYTES dynamic bytes
 

@@ -415,6 +415,10 @@ __device__ __forceinline__ void store8_unaligned(uint8_t *dst, uint32_t lo, uint
     *(Unaligned64 *)dst = v;
 }
 
+// the result-store policy in a kernel's AUX_ word (bits 4 and 5; the low four bits are the cache policy of the column's DMA):
+// 0 plain, 1 non-temporal, 2 write-through (sc1)
+constexpr int store_policy_of(int aux) { return (aux & 32) ? 2 : ((aux & 16) ? 1 : 0); }
+
 // NT: 1 = non-temporal store (the bitmap is written once and not re-read by this kernel); 2 = sc1 write-through
 // store (experiment, 16-byte form only)
 template <int WORDS, int NT = 0> __device__ __forceinline__ void store_words(uint8_t *dst, const uint32_t (&v)[WORDS])
@@ -519,6 +523,11 @@ __device__ __forceinline__ void hits_finalize(const ScanArgs &a, uint32_t P, int
 // lane's 8 counts (<= 64 each) are packed four to a dword in 16-bit fields, two wave reductions sum them
 // (<= 4096 per field), lane 0 adds the 8 sums to per-block counters in LDS, and the block flushes those to the
 // replicated global totals once, at the end.
+// (every thread of the block clears the counters first; a barrier separates that from the first add)
+__device__ __forceinline__ void block_hits_clear(uint32_t *s_hits)
+{
+    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+}
 __device__ __forceinline__ void block_hits_add8(uint32_t *s_hits, uint32_t kbase, uint32_t P, const uint32_t (&cnt)[8], int lane)
 {
     uint32_t p0 = cnt[0] | (cnt[1] << 16), p1 = cnt[2] | (cnt[3] << 16), p2 = cnt[4] | (cnt[5] << 16), p3 = cnt[6] | (cnt[7] << 16);

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_where_lut_kernel(WhereAr
     constexpr int WORDS = G::WORDS;
     constexpr int GROUPS = VPL / 8;
     constexpr int AUX = AUX_ & 15;
-    constexpr int NTS = (AUX_ & 32) ? 2 : ((AUX_ & 16) ? 1 : 0); // result stores: 1 non-temporal, 2 write-through (sc1)
+    constexpr int NTS = store_policy_of(AUX_); // result stores: 1 non-temporal, 2 write-through (sc1)
     constexpr int NRES = LAYOUT == 0 ? 8 * WORDS : GROUPS * 2;   // result dwords per lane, tile and pass
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     __shared__ __attribute__((aligned(16))) uint8_t lut_static[(MULTI || W::TABLE_BYTES < 16) ? 16 : W::TABLE_BYTES];
@@ -162,8 +162,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_where_lut_kernel(WhereAr
     __shared__ uint32_t s_hits[MULTI ? kMaxKeys : 1];          // MULTI: per-block hit counters (block_hits_add8)
     __shared__ uint32_t s_carry[2 * kWavesPerBlock];
     __shared__ __attribute__((aligned(16))) uint8_t stage[(LAYOUT == 1 && !MULTI) ? kWavesPerBlock : 1][(LAYOUT == 1 && !MULTI) ? GROUPS * 8 * 64 : 16];
-    if constexpr (MULTI)
-        for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    if constexpr (MULTI) block_hits_clear(s_hits);
 
     const ScanArgs &s = a.s;
     const int lane = threadIdx.x & 63;
@@ -512,7 +511,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_where_chain_kernel(Where
     constexpr int AUX = AUX_ & 15;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][G::LDS_BYTES];
     __shared__ uint32_t s_hits[kMaxKeys];
-    for (uint32_t k = threadIdx.x; k < (uint32_t)kMaxKeys; k += kBlockThreads) s_hits[k] = 0;
+    block_hits_clear(s_hits);
     __syncthreads();
 
     const ScanArgs &s = a.s;

@@ -1,6 +1,7 @@
 // where_group.hip -- instantiates the kernels of predicates/where.hpp for widths MI355_WLO..MI355_WHI and exports one
 // launcher per group.  Compiled 8 times (4 widths each), like width_group.hip.
 #include "../launch_util.hpp"
+#include "../shared_plan.hpp"
 #include "where_dispatch.hpp"
 
 #ifndef MI355_WLO
@@ -11,7 +12,7 @@ namespace mi355 {
 
 namespace {
 
-constexpr int kWhereVpl = scan_vpl(0, kModeShared); // 64 values per lane and tile, as the equality shared scans
+constexpr int kWhereVpl = kSharedVpl; // 64 values per lane and tile, as the equality shared scans
 
 // ---- the fit rule ----------------------------------------------------------------------------
 // The multi-pass table kernel keeps ceil(P / 8) full tables of max(2^c, 4) bytes in dynamic LDS next to its static part:
@@ -23,16 +24,22 @@ template <int C> constexpr size_t where_table_bytes(uint32_t P)
 {
     return ((size_t)((P + 7) / 8) * WhereLutGeom<C>::TABLE_BYTES + 15) / 16 * 16;
 }
-template <int C> constexpr bool where_tables_fit(uint32_t P) { return where_table_bytes<C>(P) + where_static_lds<C>() <= 160 * 1024; }
+template <int C> constexpr bool where_tables_fit(uint32_t P) { return where_table_bytes<C>(P) + where_static_lds<C>() <= kCuLds; }
 
-// blocks per CU of the table kernels: shared_lut_kernel's rule (one block per CU, two for small tiles and for the linear
-// layout), as far as the tables leave room
+// blocks per CU of the table kernels: shared_lut_kernel's rule (lut_want_bpc), as far as the tables leave room
 template <int C> int where_lut_bpc(const WhereReq &r, bool linear, size_t lds_per_block)
 {
-    const int want = r.l.max_blocks_per_cu > 0 ? r.l.max_blocks_per_cu : ((ScanGeom<C, kWhereVpl>::TILE_BYTES < 4096 || linear) ? 2 : 1);
-    int fit = (int)((160 * 1024) / lds_per_block);
+    const int want = lut_want_bpc(ScanGeom<C, kWhereVpl>::TILE_BYTES, linear, r.l.max_blocks_per_cu);
+    int fit = (int)(kCuLds / lds_per_block);
     if (fit < 1) fit = 1;
     return want < fit ? want : fit;
+}
+
+// one launch of a where-kernel: the dynamic-LDS limit (max_dyn > 0), then the launch (the kernels read no flag bits)
+template <auto Kernel> void launch_where_kernel(const WhereReq &r, dim3 grid, size_t dyn_lds = 0, int max_dyn = 0)
+{
+    if (max_dyn > 0) allow_dynamic_lds<Kernel>(max_dyn, r.l.device);
+    MI355_LAUNCH(r.l, 0, Kernel, grid, dim3(kBlockThreads), dyn_lds, r.l.stream, r.w);
 }
 
 template <int C> hipError_t launch_where(const WhereReq &r)
@@ -52,18 +59,16 @@ template <int C> hipError_t launch_where(const WhereReq &r)
             const int spol = one_pass_store_policy((s.n / 8) * P, r.l.scan_nt_stores); // 0 plain, 1 nt, 2 sc1
             const size_t per_block = 4 * G::LDS_BYTES + WhereLutGeom<C>::TABLE_BYTES + (linear ? 4 * (VPL / 8) * 8 * 64 : 0) + 512;
             const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, per_block), r.l.num_cus));
-            if (linear && spol == 1)
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 18, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
-            else if (linear && spol == 2)
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 34, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
-            else if (linear)
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 1, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
-            else if (spol == 1)
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 18, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
-            else if (spol == 2)
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 34, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
-            else
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 0, false>), grid, dim3(kBlockThreads), 0, r.l.stream, r.w);
+            auto go = [&](auto layout) {
+                constexpr int LAYOUT = decltype(layout)::value;
+                if (spol == 1)
+                    launch_where_kernel<shared_where_lut_kernel<C, 18, VPL, LAYOUT, false>>(r, grid);
+                else if (spol == 2)
+                    launch_where_kernel<shared_where_lut_kernel<C, 34, VPL, LAYOUT, false>>(r, grid);
+                else
+                    launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, LAYOUT, false>>(r, grid);
+            };
+            linear ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 0>{});
             return launch_status(r.l);
         }
         if constexpr (where_tables_fit<C>(9)) // (c = 16: two tables never fit, the multi-pass form is not instantiated)
@@ -72,25 +77,20 @@ template <int C> hipError_t launch_where(const WhereReq &r)
             // scans of more than 8 keys)
             const bool nt_stores = multi_pass_nt_stores((s.n / 8) * P, r.l.scan_nt_stores);
             const size_t dyn = where_table_bytes<C>(P);
-            const int max_dyn = (int)(160 * 1024 - where_static_lds<C>());
+            const int max_dyn = (int)(kCuLds - where_static_lds<C>());
             const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, dyn + where_static_lds<C>()), r.l.num_cus));
-            if (linear) {
-                allow_dynamic_lds<shared_where_lut_kernel<C, 2, VPL, 1, true>>(max_dyn, r.l.device);
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 1, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
-            } else if (nt_stores) {
-                allow_dynamic_lds<shared_where_lut_kernel<C, 18, VPL, 0, true>>(max_dyn, r.l.device);
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 18, VPL, 0, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
-            } else {
-                allow_dynamic_lds<shared_where_lut_kernel<C, 2, VPL, 0, true>>(max_dyn, r.l.device);
-                MI355_LAUNCH(r.l, 0, (shared_where_lut_kernel<C, 2, VPL, 0, true>), grid, dim3(kBlockThreads), dyn, r.l.stream, r.w);
-            }
+            if (linear)
+                launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, 1, true>>(r, grid, dyn, max_dyn);
+            else if (nt_stores)
+                launch_where_kernel<shared_where_lut_kernel<C, 18, VPL, 0, true>>(r, grid, dyn, max_dyn);
+            else
+                launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, 0, true>>(r, grid, dyn, max_dyn);
             return launch_status(r.l);
         }
     }
     if constexpr (C >= 11) { // (at c <= 10 every list fits the tables)
         static const int bpc = blocks_per_cu(shared_where_chain_kernel<C, 2, VPL>);
-        MI355_LAUNCH(r.l, 0, (shared_where_chain_kernel<C, 2, VPL>), dim3(grid_for(ntiles, cap_bpc(bpc, r.l.max_blocks_per_cu), r.l.num_cus)),
-                     dim3(kBlockThreads), 0, r.l.stream, r.w);
+        launch_where_kernel<shared_where_chain_kernel<C, 2, VPL>>(r, dim3(grid_for(ntiles, cap_bpc(bpc, r.l.max_blocks_per_cu), r.l.num_cus)));
         return launch_status(r.l);
     }
     return hipErrorInvalidValue;

@@ -116,6 +116,17 @@ def shared_where_kernel(c: int, P: int, layout: str = "per_predicate", with_hits
     return s.decode()
 
 
+def semi_join_kernel(c: int, set_bits: int) -> str:
+    """kernel family ScanEngine.semi_join launches for a set of set_bits bits at width c (mi355_semijoin_kernel; arithmetic
+    only, needs no device): 'semijoin_lds_kernel' | 'semijoin_global_kernel'"""
+    if not 0 <= int(set_bits) <= 1 << 32:
+        raise ValueError((c, set_bits))
+    s = lib().mi355_semijoin_kernel(c, int(set_bits))
+    if s is None:
+        raise ValueError((c, set_bits))
+    return s.decode()
+
+
 class PackedColumn:
     """A bit-packed column resident in HBM: `n` values of `c` bits, reference stream format."""
 
@@ -335,6 +346,30 @@ class ScanEngine:
                                       1 if negate else 0, and_mask.data_ptr() if and_mask is not None else None,
                                       bitmap.data_ptr(), hits.data_ptr()))
         return bitmap, hits
+
+    def semi_join(self, col: PackedColumn, set_bitmap: Optional[torch.Tensor], set_bits: int, negate: bool = False,
+                  and_mask: Optional[torch.Tensor] = None, bitmap=None, want_hits: bool = True):
+        """bitmap[i] = (value_i < set_bits and bit value_i of set_bitmap) (NOT IN with negate=True) [& and_mask[i]] -> (bitmap,
+        hits): `fk IN (SELECT pk FROM dim WHERE ...)` with set_bitmap the result bitmap of a scan over the set_bits rows of
+        `dim`, consumed where it lies (uint8 device tensor of at least ceil(set_bits/8) bytes; None only with set_bits == 0).
+        Capturable into a graph: the set is read at every replay.  bitmap=False: count only, no bitmap is stored (returns
+        (None, hits)); want_hits=False: no count (returns (bitmap, None))."""
+        set_bits = int(set_bits)
+        if not 0 <= set_bits <= 1 << 32:
+            raise ValueError(f"set_bits {set_bits} outside 0..2^32")  # (ctypes would wrap it silently)
+        if set_bitmap is None:
+            assert set_bits == 0
+        else:
+            assert set_bitmap.dtype == torch.uint8 and set_bitmap.numel() >= (set_bits + 7) // 8
+        count_only = bitmap is False
+        assert not (count_only and not want_hits), "neither a bitmap nor a count asked for"
+        if bitmap is None:
+            bitmap = self.alloc_bitmap(col.n)
+        hits = torch.empty(1, dtype=torch.int64, device=self._dev) if want_hits else None
+        check(lib().mi355_semijoin_dev(self._ctx, col.data.data_ptr(), col.n, col.c, set_bitmap.data_ptr() if set_bitmap is not None else None,
+                                       set_bits, 1 if negate else 0, and_mask.data_ptr() if and_mask is not None else None,
+                                       None if count_only else bitmap.data_ptr(), hits.data_ptr() if want_hits else None))
+        return (None if count_only else bitmap), hits
 
     def bitmap_combine(self, op: str, a: torch.Tensor, b: torch.Tensor, n: int, out: Optional[torch.Tensor] = None):
         if out is None:

@@ -70,13 +70,7 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
         if (!known) ctx->llc_prev[0] = nullptr;
     } else
         ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
-    // the A/B switches of the shared scans (bits 0-8) never reach the selection kernels, whose switches live in bits 9-12 of
-    // the option and arrive as their bits 1-4: two TIMING ablations (2 no expansion, 4 no look-back: wrong ids by construction)
-    // and two A/B switches of select_kernel's chunk hand-out (8 chunks dealt out by block index as in round 2, 16 no barrier
-    // per generation).  Option bits 13.. are further switches of the shared scans; they arrive as their bits 9.. and never reach
-    // the selection.  Option bit 16 (kernel bit 12) is read nowhere and stays out; kernel bits 17 and 20 are the launcher's own.
-    // (tests/test_kernel_paths.py maps every kernel-side test back through these two expressions.)
-    r.scan.flags = r.op == kOpSelect ? ((ctx->kernel_flags >> 8) & 0x1eu) : ((ctx->kernel_flags & 0x1ffu) | ((ctx->kernel_flags >> 4) & 0xdee00u));
+    r.scan.flags = kernel_switch_word(ctx->kernel_flags, r.op == kOpSelect); // (switches.hpp: the selection sees only its own)
     r.scan.scratch = ctx->kernel_scratch;
     if (r.max_blocks_per_cu == 0 && !ctx->tuned_bpc.empty()) {
         const bool scan = r.op == kOpScanEq || r.op == kOpScanRange;

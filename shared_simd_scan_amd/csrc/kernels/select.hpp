@@ -104,9 +104,10 @@ __global__ __launch_bounds__(kBlockThreads, 1) void select_kernel(ScanArgs a)
         tc.template issue<AUX>(a.packed, t, lds_wave, lane);
     };
 
-    // (A/B switches, timing only -- the results are the same: flags bit 3 = chunks dealt out by block index as in round 2,
-    // which is only safe while the whole grid is resident; bit 4 = no barrier per generation, with bit 3 only)
-    const bool by_index = (a.flags & 8u) != 0, no_barrier = (a.flags & 24u) == 24u;
+    // (A/B switches, timing only -- the results are the same: kSelByBlockIndex = chunks dealt out by block index as in round 2,
+    // which is only safe while the whole grid is resident; kSelNoBarrier = no barrier per generation, with kSelByBlockIndex only)
+    const bool by_index = (a.flags & kSelByBlockIndex) != 0,
+               no_barrier = (a.flags & (kSelByBlockIndex | kSelNoBarrier)) == (kSelByBlockIndex | kSelNoBarrier);
     const unsigned long long gen_stride = (unsigned long long)gridDim.x * kWavesPerBlock;
     // the block's first two generations: one claim of 4 chunks each (two dependent atomics: the second lands behind the
     // first claims of the blocks that started at about the same time, so generation 1 lies mostly above generation 0)
@@ -410,7 +411,7 @@ __global__ __launch_bounds__(kBlockThreads, 1) void select_kernel(ScanArgs a)
     // round trip passes behind the remaining tiles -- 0.267 -> 0.294 ms at 1e9 x 9 bit, 1/512: the branch and the 32 live
     // registers in the tile loop cost the decode more than the poll's latency.)
     auto finish = [&](uint64_t q, unsigned long long q_hits, int ntiles_q, uint32_t(*pk)[64 * WORDS]) {
-        const bool look_back = !(a.flags & 4u), want_ids = q_hits && !(a.flags & 2u); // (flags: tuning aids, ablations)
+        const bool look_back = !(a.flags & kSelNoLookBack), want_ids = q_hits && !(a.flags & kSelNoExpansion); // (flags: tuning aids, ablations)
         unsigned long long s[kSelectWindow];
         if (look_back && q > 0) poll_issue((int64_t)q - 1, s);
         ChunkWords cw;

@@ -431,7 +431,7 @@ __global__ __launch_bounds__(kSel2Waves * 64, 1) void select2_kernel(ScanArgs a)
         } else if (exp_active) {
             // ---- expand the chunk decoder d parked in the generation before ------------------------------------------------------
             const int pb = buf ^ 1;
-            const bool look_back = !(a.flags & 4u); // (flags: timing ablations)
+            const bool look_back = !(a.flags & kSelNoLookBack); // (flags: timing ablations)
             const bool looker = wave == D;          // first expander of decoder 0: the block's look-back
             unsigned long long before = 0;
             if (looker) {
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kSel2Waves * 64, 1) void select2_kernel(ScanArgs a)
                 const unsigned long long q_hits = uniform64(s_hits[d][pb]);
                 const int ntiles_q = __builtin_amdgcn_readfirstlane(s_ntiles[d][pb]);
                 uint32_t(*const pk)[64 * WORDS] = parked[d][pb];
-                const bool want_ids = q_hits && !(a.flags & 2u);
+                const bool want_ids = q_hits && !(a.flags & kSelNoExpansion);
                 // a sparse chunk (the usual case of a selective predicate) is its first expander's alone: no tile prefixes, no
                 // hand-over, the other expander leaves the SIMD to the decoder
                 const bool sparse_chunk = q_hits <= 64ull * K;

@@ -882,7 +882,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_wide_kernel(ScanArgs a)
         const uint64_t next = tile + stride;
         if (next < tc.ntiles) tc.template issue<AUX>(a.packed, next, lds_wave, lane);
         const bool full = tile < tc.nfull;
-        behind = (full && !(a.flags & 1u)) ? stores_per_tile : 0; // (a tail tile is a wave's last: nothing waits behind it)
+        behind = (full && !(a.flags & kSwDrainEveryTile)) ? stores_per_tile : 0; // (a tail tile is a wave's last: nothing waits behind it)
         uint32_t xs[VPL];
         extract_all<C, VPL, 0, G::LANE_DWORDS>(w, xs);
         const int64_t left = (int64_t)(tc.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL;
@@ -1095,7 +1095,7 @@ __global__ __launch_bounds__(kBlockThreads) void shared_wide2_kernel(ScanArgs a)
         const uint64_t next = tile + stride;
         if (next < tc.ntiles) tc.template issue<AUX>(a.packed, next, lds_wave, lane);
         const bool full = tile < tc.nfull;
-        behind = (full && !(a.flags & 1u)) ? P : 0;
+        behind = (full && !(a.flags & kSwDrainEveryTile)) ? P : 0;
         uint32_t xs[VPL];
         extract_all<C, VPL, 0, G::LANE_DWORDS>(w, xs);
         const int64_t left = (int64_t)(tc.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL;
@@ -1108,9 +1108,9 @@ __global__ __launch_bounds__(kBlockThreads) void shared_wide2_kernel(ScanArgs a)
             }
         }
 
-        // (flags bit 2, experiment: every wave starts its round-robin over the 32-key rounds at a different round, so the
+        // (kSwRotateRounds, experiment: every wave starts its round-robin over the 32-key rounds at a different round, so the
         // waves of the lock-stepped grid do not all write the same 32 output streams at the same time)
-        const uint32_t rot = (RC != 2 && (a.flags & 4u)) ? (uint32_t)((blockIdx.x * kWavesPerBlock + wave) % npass32) : 0u;
+        const uint32_t rot = (RC != 2 && (a.flags & kSwRotateRounds)) ? (uint32_t)((blockIdx.x * kWavesPerBlock + wave) % npass32) : 0u;
         auto do_round = [&](const uint32_t pi) __attribute__((always_inline)) {
             const uint32_t p32 = pi + rot < npass32 ? pi + rot : pi + rot - npass32;
             const uint32_t *table = lut + p32 * L::TABLE_DWORDS;
@@ -1313,8 +1313,8 @@ __global__ __launch_bounds__(kBlockThreads) void shared_linear_kernel(ScanArgs a
     // stores) and leaves as ALIGNED 16-byte stores; only the < 16 bytes in front of the first and behind the last aligned
     // chunk go out as single bytes.  Unaligned 16-byte global stores (every piece of such a row) cost a quarter to a third of
     // the kernel: 2.5e8 x 9 bit with hit counts, P = 63 / 64: 2.9 / 3.9 TB/s, 257 / 256: 3.5 / 4.5, 385 / 384: 2.9 / 4.0.
-    // The image lives in DYNAMIC LDS behind the tables, kLinearImageBytes per wave, and only when the launcher asks for it (flags bit
-    // 20): as a static array it cost every launch of this kernel 8.4 KiB and with them a resident block at many key counts
+    // The image lives in DYNAMIC LDS behind the tables, kLinearImageBytes per wave, and only when the launcher asks for it
+    // (kSetImage): as a static array it cost every launch of this kernel 8.4 KiB and with them a resident block at many key counts
     // (aligned rows, same box: P = 128 0.96 -> 1.21 ms, P = 192 1.38 -> 1.83).
     __shared__ uint32_t s_hits[kMaxKeys];
     constexpr bool HIST = C <= 12; // hit counts by histogram of the values (see shared_wide2_kernel), else packed byte counters
@@ -1338,12 +1338,12 @@ __global__ __launch_bounds__(kBlockThreads) void shared_linear_kernel(ScanArgs a
     // Where it pays: two lanes per row (P = 33 .. 63: a step's image is 32 rows, up to 2 KiB -- same box, with hit counts, P = 57 / 63:
     // 2.81 / 2.86 -> 3.50 / 3.77 TB/s).  One lane per row loses (P = 9: 2.80 -> 1.88, P = 24: 3.93 -> 3.62: small images, the
     // write -> wait -> read -> store chain per step is not hidden), and so do three and more (P = 65: 2.38 -> 2.02, 257: 3.15 -> 2.58:
-    // 64 mod T idle lanes, images of 1.3 KiB and more steps per tile).  (flags bit 14: never, for A/B)
+    // 64 mod T idle lanes, images of 1.3 KiB and more steps per tile).  (kSwNoImage: never, for A/B)
     // Single-table widths only: at c = 17 the image costs the kernel a resident block (P = 47: 2.62 -> 2.32 TB/s, 63: 2.96 -> 2.82).
-    // Copying the image out a step late (below) left every one of these figures where it was -- with it and flags bit 19 (the image at
+    // Copying the image out a step late (below) left every one of these figures where it was -- with it and kSwImageAnyLength (the image at
     // every T) P = 9 / 17 with hit counts run at 0.67 / 0.72 x, P = 300 / 511 at 0.75 / 0.70 x of the direct stores: the image's LDS
     // traffic (unaligned ds_write_b128 + the read back), not a wait, is what it costs.
-    const bool staged = RP == 1 && (a.flags & 0x100000u); // (the launcher's rule: linear_image_wanted())
+    const bool staged = RP == 1 && (a.flags & kSetImage); // (the launcher's rule: linear_image_wanted())
     uint8_t *const ostage_wave = mi355_dyn_lds + T * (uint32_t)(L::TABLE_DWORDS * 4) + (uint32_t)wave * kLinearImageBytes;
     // The image of step s leaves during step s + 1: its LDS reads are issued in front of that step's decode (a wave's LDS
     // operations execute in order, so they see step s's pieces and are not disturbed by step s + 1's, which follow them),
@@ -1640,8 +1640,8 @@ __global__ __launch_bounds__(kBlockThreads) void shared_linear2_kernel(ScanArgs 
     const uint32_t Tf = P / 32, R = P % 32;                        // full tables; keys of the short last one
     const uint32_t T = Tf + (R ? 1u : 0u);
     // the short piece rides on the lane of the row's LAST full piece (Tf = 1; behind two to five full tables when it is short
-    // enough for the launcher to ask for it: flags bit 17) ...
-    const bool attached = R != 0 && (Tf == 1 || (Tf >= 2 && (a.flags & 0x20000u)));
+    // enough for the launcher to ask for it: kSetShortAttached) ...
+    const bool attached = R != 0 && (Tf == 1 || (Tf >= 2 && (a.flags & kSetShortAttached)));
     const bool dedicated = R != 0 && !attached;                    // ... or gets steps of its own
     const bool aligned16 = (P & 15u) == 0;                         // every full piece starts on a 16-byte boundary
     const bool use_hist = HIST && P >= 128;

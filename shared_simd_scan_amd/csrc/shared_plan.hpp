@@ -32,7 +32,7 @@ struct SharedPlan {
     bool big = false;       // wider table digits (WideLutGeom<C, true>)
     int store = 0;          // result stores: 0 plain, 1 non-temporal, 2 write-through
     size_t dyn_lds = 0;     // dynamic LDS bytes
-    uint32_t set_flags = 0; // the launcher's own flag bits: 0x20000 short last table attached, 0x100000 aligned output image
+    uint32_t set_flags = 0; // the launcher's own switch for the kernel: kSetShortAttached or kSetImage (switches.hpp)
     SharedPlan &lds(size_t bytes) { dyn_lds = bytes; return *this; }
     SharedPlan &stores(int policy) { store = policy; return *this; }
     SharedPlan &counters(int rc_, bool big_) { rc = rc_, big = big_; return *this; }
@@ -96,13 +96,13 @@ inline int lut_want_bpc(int tile_bytes, bool linear, int max_blocks_per_cu)
 // wave-step covers 64 / Tf rows instead of 64 / (Tf + 1) and pays the short piece's instructions with 1 / Tf of the lanes in
 // use.  Measured at every Tf = 2 .. 8, 12, 15 and R = 1 .. 31 (2.5e8 x 9 bit, profiles/r03_linear_attach_ab.txt): where the row
 // gain is >= 1.19 x it wins at (almost) every R -- 1.0 - 1.4 x; where it is 1.10 .. 1.18 x only for R <= 8; where the row
-// count does not change (Tf = 11, 13 .. 15, ...) it loses 10 - 20 %.  (flags bit 16: never, bit 18: always, for A/B)
+// count does not change (Tf = 11, 13 .. 15, ...) it loses 10 - 20 %.  (kSwShortNeverAttached / kSwShortAlwaysAttached, for A/B)
 inline bool attach_short(unsigned P, unsigned flags, bool hits)
 {
     const unsigned Tf = P / 32, R = P % 32;
     if (Tf < 2 || R == 0) return false;
-    if (flags & 0x40000u) return true;
-    if (flags & 0x10000u) return false;
+    if (flags & kSwShortAlwaysAttached) return true;
+    if (flags & kSwShortNeverAttached) return false;
     const unsigned rows_attached = 64 / Tf, rows_own_lane = 64 / (Tf + 1);
     if (rows_attached * 100 >= rows_own_lane * 119) return !(Tf == 3 && R > 24);
     // (Tf = 7 with hit counts: the old mapping's eight lanes per row count one value each with a single LDS atomic)
@@ -122,8 +122,8 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
     const int max_bpc = r.max_blocks_per_cu;
     const uint64_t out_bytes = (r.scan.n / 8) * P; // the P bitmaps together
 
-    // ---- 1. two keys: the equality scan's decode twice (flags bit 5: the LUT kernel, A/B)
-    if (P == 2 && !(flags & 32u)) {
+    // ---- 1. two keys: the equality scan's decode twice (kSwPairOnLut: the LUT kernel, A/B)
+    if (P == 2 && !(flags & kSwPairOnLut)) {
         // per-predicate: the scan's geometry (128 values per lane at c <= 16: a 16-byte store per key and lane); linear:
         // 64 values per lane, so that the lane's 16 row bytes are ONE store and an instruction writes 1 KiB of whole
         // lines (with 128 the lane's 32 bytes left as two instructions of half lines: write-through stores turned
@@ -144,7 +144,7 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
             .stores(one_pass_store_policy(out_bytes, r.scan_nt_stores));
     }
 
-    // ---- 3. linear rows of 32 .. 40 keys: the per-predicate machinery + an LDS stage (shared_linear3_kernel; flags bit 13: the
+    // ---- 3. linear rows of 32 .. 40 keys: the per-predicate machinery + an LDS stage (shared_linear3_kernel; kSwNoLinear3: the
     // row-per-lane kernels below, for A/B).  Hit counts in registers: one round (P <= 32) or two packed.  Where it pays
     // (2.5e8 rows, TB/s with hit counts, against the row-per-lane kernels on the same box): c = 9, P = 32 / 33 / 40:
     // 4.67 / 3.54 / 3.52 against 4.05 / 3.29 / 3.24; c = 5, P = 32: 4.49 against 3.28; c = 12: 4.54 against 4.06; c = 17:
@@ -152,9 +152,9 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
     // 4.33, P = 24 / 31 equal), a long second round (its 32-byte pieces complete the first round's half-written lines a
     // whole round later: P = 48 3.01 against 3.41, P = 64 2.29 against 3.94), and widths whose tiles leave room for one
     // block per CU only (c = 25, P = 32: 2.95 against 4.40).
-    if (linear && P >= 32 && P <= 40 && !(flags & 0x2000u) && 2 * (wide_table_bytes<C>(P) + linear3_fixed_lds<C>()) <= kCuLds) {
+    if (linear && P >= 32 && P <= 40 && !(flags & kSwNoLinear3) && 2 * (wide_table_bytes<C>(P) + linear3_fixed_lds<C>()) <= kCuLds) {
         bool big = false;
-        if constexpr (kBigWidth) big = !(flags & 0x200u) && 2 * (wide_table_bytes<C, true>(P) + linear3_fixed_lds<C>()) <= kCuLds;
+        if constexpr (kBigWidth) big = !(flags & kSwByteDigits) && 2 * (wide_table_bytes<C, true>(P) + linear3_fixed_lds<C>()) <= kCuLds;
         const size_t dyn3 = big ? wide_table_bytes<C, true>(P) : wide_table_bytes<C>(P);
         const int fit = (int)(kCuLds / (dyn3 + linear3_fixed_lds<C>()));
         return make_plan(kFormLinear3, cap_bpc(fit > 2 ? 2 : (fit < 1 ? 1 : fit), max_bpc)).lds(dyn3).counters(hits ? (P <= 32 ? 1 : 2) : 0, big);
@@ -162,15 +162,15 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
 
     // linear rows of 9 .. 1024 keys: lanes in memory order (shared_linear_kernel).  It needs two blocks per CU to hide its
     // lookups: tables too big for that -- P = 1024 at c <= 10 -- stay on the per-group kernel unless hit counts are
-    // wanted (2.5e8 x 9 bit, P = 1024: 13.5 against 10.2 ms without, 15.6 against 17.8 with).  (flags bit 1: the older kernels, A/B)
+    // wanted (2.5e8 x 9 bit, P = 1024: 13.5 against 10.2 ms without, 15.6 against 17.8 with).  (kSwPerGroupKernels: the older kernels, A/B)
     // Digit-table widths (c > 10) leave it to the per-group kernel beyond 320 keys (beyond 160 without hit counts at c > 16):
     // every lane of a row decodes the row again and looks up ceil(c/8) digits, and the tables leave room for two blocks
     // per CU only (2.5e8 rows, with / without hit counts, TB/s, shared_linear_kernel against the per-group kernel: c = 13,
     // P = 300: 2.6 / 2.9 against 2.2 / 2.2, P = 400: 2.1 / 2.3 against 2.4 / 2.7, P = 600: 1.7 / 1.8 against 2.4 / 2.6;
     // c = 17, P = 150: 2.6 / 2.8 against 1.4 / 1.8, P = 200: 2.6 / 2.8 against 1.5 / 3.0, P = 300: 2.1 / 2.2 against 1.5 / 2.5;
     // c = 9, P = 300: 3.6 / 4.1 against 2.2 / 2.3).
-    const bool lin_pays = C <= 10 || (C <= 16 ? P <= 320 : P <= (hits ? 320u : 160u)) || (flags & 128u); // (bit 7: always, A/B)
-    const bool lin_rows = linear && lut_fits<C, VPL>(P) && !(flags & 2u) && lin_pays &&
+    const bool lin_pays = C <= 10 || (C <= 16 ? P <= 320 : P <= (hits ? 320u : 160u)) || (flags & kSwLinearAnyWidth); // (always, A/B)
+    const bool lin_rows = linear && lut_fits<C, VPL>(P) && !(flags & kSwPerGroupKernels) && lin_pays &&
                           (2 * (wide_table_bytes<C>(P) + lut_static_lds<C, VPL>()) <= kCuLds || (hits && WideLutGeom<C>::SINGLE));
 
     // ---- 4. linear rows of fewer than ~200 keys without hit counts, where the row-per-lane kernels do not run: byte-entry
@@ -185,11 +185,11 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
     // (16 v_cmp + v_addc per value beat three or four lookups + ANDs per value in shared_wide2_kernel at ONE wave per SIMD).
     // shared_wide3_kernel turns that around (2.5e8 rows, with hit counts, TB/s, tables against chain: c = 17, P = 16: 4.39
     // against 2.92; c = 21: 3.61 against 3.27; c = 29: 4.77 against 3.56, P = 24: 4.74), so the chain keeps only the key
-    // counts whose tables do not fit (flags bit 10: round 2's rule, for A/B).
-    const bool chain_pays = !linear && C >= 17 && P <= (C >= 25 ? 24u : 16u) && (flags & 0x400u);
+    // counts whose tables do not fit (kSwChainRuleRound2: round 2's rule, for A/B).
+    const bool chain_pays = !linear && C >= 17 && P <= (C >= 25 ? 24u : 16u) && (flags & kSwChainRuleRound2);
 
-    // ---- 5. more keys than the tables hold: compare chain, ceil(P/8) passes over the registers (flags bit 6: always, for A/B)
-    if (!lut_fits<C, VPL>(P) || (flags & 64u) || chain_pays) return make_plan(kFormChain, max_bpc > 0 ? max_bpc : 0);
+    // ---- 5. more keys than the tables hold: compare chain, ceil(P/8) passes over the registers (kSwCompareChain: always, for A/B)
+    if (!lut_fits<C, VPL>(P) || (flags & kSwCompareChain) || chain_pays) return make_plan(kFormChain, max_bpc > 0 ? max_bpc : 0);
 
     // ---- everything below: one dword-entry lookup table per 32 keys, in dynamic LDS
     const size_t dyn = wide_table_bytes<C>(P);
@@ -199,51 +199,51 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
         const int want = max_bpc > 0 ? max_bpc : 4;
         // P = 16: two rows per 32-byte piece only with the digit tables (c > 10: 4.0 / 4.8 TB/s against 3.2 / 4.2 with one
         // row per piece at c = 12); at c <= 10 one row per piece wins (c = 5: 3.0 / 4.7 against 2.0 / 4.1, c = 9: 3.9 /
-        // 4.8 against 3.5 / 4.9 with / without hit counts).  (flags bit 4: one row per piece everywhere, for A/B)
-        if (P == 16 && C > 10 && !(flags & 16u)) return make_plan(kFormLinearTwoRows, want).lds(dyn);
-        // everything else: full tables in memory order, the short last table on its own (shared_linear2_kernel; flags
-        // bit 8: round 2's kernel, which gives the short table a whole lane per row, for A/B)
+        // 4.8 against 3.5 / 4.9 with / without hit counts).  (kSwP16OneRowPerPiece: everywhere, for A/B)
+        if (P == 16 && C > 10 && !(flags & kSwP16OneRowPerPiece)) return make_plan(kFormLinearTwoRows, want).lds(dyn);
+        // everything else: full tables in memory order, the short last table on its own (shared_linear2_kernel;
+        // kSwLinearRound2: round 2's kernel, which gives the short table a whole lane per row, for A/B)
         // shared_linear2_kernel (the short last table on the full piece's lane / in steps of its own) is the product only for
         // rows below 32 keys without hit counts (2.5e8 x 9 bit, same box: P = 12: 4.09 against 3.77 TB/s; with hit counts
         // 2.87 against 3.43).  For rows of 33 .. 63 keys it beat round 2's kernel (P = 33: 3.10 against 2.59) until that kernel
         // learnt to write such rows through an aligned LDS image (P = 47 / 52 / 56: 3.02 / 3.30 / 3.46 against 2.82 / 2.84 /
-        // 2.85; flags bit 15 brings it back for A/B), and its short-table steps LOSE behind two or more full tables -- P = 100:
+        // 2.85; kSwLinear2Short brings it back for A/B), and its short-table steps LOSE behind two or more full tables -- P = 100:
         // 2.26 against 3.18, P = 300: 2.45 against 3.58: a step that writes 4 bytes of each of 64 rows is 64 partial-line
         // transactions, where the old mapping's short lane sits in the same store instruction as its row's full pieces.
         // Rows of 65 and more keys with a short last table: attach_short() above decides between the two mappings.
         const bool attached = attach_short(P, flags, hits);
-        if (!(flags & 256u) && (((flags & 0x8000u) && P / 32 == 1 && P % 32 >= 1 && P % 32 <= 24) || (P < 32 && !hits) || attached))
-            return make_plan(kFormLinear2, want).lds(dyn).flag(attached ? 0x20000u : 0u);
+        if (!(flags & kSwLinearRound2) && (((flags & kSwLinear2Short) && P / 32 == 1 && P % 32 >= 1 && P % 32 <= 24) || (P < 32 && !hits) || attached))
+            return make_plan(kFormLinear2, want).lds(dyn).flag(attached ? kSetShortAttached : 0u);
         // rows of 33 .. 63 keys whose length is not a multiple of 16 bytes, single-table widths: through the wave-private
-        // aligned output image (dynamic LDS behind the tables; flags bit 14: never, bit 19: at every row length, A/B)
+        // aligned output image (dynamic LDS behind the tables; kSwNoImage: never, kSwImageAnyLength: at every row length, A/B)
         const size_t with_image = dyn + (size_t)kWavesPerBlock * kLinearImageBytes;
-        const bool image = C <= 10 && (P & 15u) != 0 && !(flags & 0x4000u) && ((P + 31) / 32 == 2 || (flags & 0x80000u)) &&
+        const bool image = C <= 10 && (P & 15u) != 0 && !(flags & kSwNoImage) && ((P + 31) / 32 == 2 || (flags & kSwImageAnyLength)) &&
                            with_image <= (size_t)shared_max_dyn_lds<C>();
-        return make_plan(kFormLinear, want).lds(image ? with_image : dyn).flag(image ? 0x100000u : 0u);
+        return make_plan(kFormLinear, want).lds(image ? with_image : dyn).flag(image ? kSetImage : 0u);
     }
 
     const int want = max_bpc > 0 ? max_bpc : 2;
     // result stores of the per-predicate bitmaps: non-temporal unless the P bitmaps together are small
     const int store = (!linear && multi_pass_nt_stores(out_bytes, r.scan_nt_stores)) ? 1 : 0;
 
-    // ---- 7. per-predicate bitmaps (flags bit 1: the per-group kernel, for A/B)
-    if (!linear && !(flags & 2u)) {
-        // Hit counts in registers (flags bit 3: per-tile wave reductions / the histogram instead, for A/B): one 32-key
+    // ---- 7. per-predicate bitmaps (kSwPerGroupKernels: the per-group kernel, for A/B)
+    if (!linear && !(flags & kSwPerGroupKernels)) {
+        // Hit counts in registers (kSwCountsByReduction: per-tile wave reductions / the histogram instead, for A/B): one 32-key
         // round in 32-bit registers (P <= 32: 2.5e8 x 9 bit, same box, P = 16 0.200 -> 0.158 ms, P = 32 0.298 -> 0.249),
         // two rounds in packed 16-bit halves (P <= 64, round 3: c = 9, P = 33 / 40 / 48 3.50 / 3.96 / 4.12 -> 4.44 / 4.81 /
         // 4.87 TB/s; not where the histogram counts -- c <= 12, P >= 64: 4.99 against 4.66).
-        // Wider digits (BIG; flags bit 9: byte digits, for A/B) at the widths of three or four byte digits while two
+        // Wider digits (BIG; kSwByteDigits: byte digits, for A/B) at the widths of three or four byte digits while two
         // blocks per CU still fit.
         const bool hist_counts = C <= 12 && P >= 64;
-        const int rc = (hits && !(flags & 8u)) ? (P <= 32 ? 1 : ((P <= 64 && !hist_counts) ? 2 : 0)) : 0;
+        const int rc = (hits && !(flags & kSwCountsByReduction)) ? (P <= 32 ? 1 : ((P <= 64 && !hist_counts) ? 2 : 0)) : 0;
         bool big = false;
-        if constexpr (kBigWidth) big = !(flags & 0x200u) && 2 * (wide_table_bytes<C, true>(P) + lut_static_lds<C, VPL>()) <= kCuLds;
+        if constexpr (kBigWidth) big = !(flags & kSwByteDigits) && 2 * (wide_table_bytes<C, true>(P) + lut_static_lds<C, VPL>()) <= kCuLds;
         const size_t bdyn = big ? wide_table_bytes<C, true>(P) : dyn;
         // a 32-value word at a time (shared_wide3_kernel: half the registers, several waves per SIMD -- what the digit-table
         // widths need, and 0-20 % ahead at c <= 10 too: 2.5e8 x 9 bit, P = 9 / 24 / 63, TB/s with / without hit counts:
         // 3.63 / 4.41, 5.13 / 5.43, 5.21 / 5.56 against 3.44 / 3.58, 4.49 / 4.58, 4.39 / 4.49) for every scan it can count:
-        // without hit counts, or up to 64 keys (flags bit 11: shared_wide2_kernel, A/B)
-        if ((!hits || rc != 0) && !(flags & 0x800u)) {
+        // without hit counts, or up to 64 keys (kSwWide2: shared_wide2_kernel, A/B)
+        if ((!hits || rc != 0) && !(flags & kSwWide2)) {
             const int waves = (rc == 0 || C <= 10) ? 3 : 2; // the kernel's launch bound
             const int fit = (int)(kCuLds / (bdyn + 4 * ScanGeom<C, 64>::LDS_BYTES + 256));
             return make_plan(kFormWide3, cap_bpc(fit > waves ? waves : (fit < 1 ? 1 : fit), max_bpc)).lds(bdyn).counters(rc, big).stores(store);
@@ -253,7 +253,7 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
         return make_plan(kFormWide2, want).lds(bdyn).counters(C <= 10 ? rc : 0, big).stores(store);
     }
 
-    // ---- 8. the per-group kernel: the linear rows it keeps (lin_pays), either layout under flags bit 1
+    // ---- 8. the per-group kernel: the linear rows it keeps (lin_pays), either layout under kSwPerGroupKernels
     return make_plan(linear ? kFormWideLinear : kFormWide, want).lds(dyn).stores(store);
 }
 

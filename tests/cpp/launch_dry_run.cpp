@@ -4,17 +4,24 @@
 // launchers only decide, report the kernel family and write the launch-record line.  The occupancy queries have no device
 // to ask and fall back to one block per CU, so the grid column means nothing here.
 //
-// stdin, one case per line:  op c P layout hits n flags shared_vpl scan_nt_stores max_blocks_per_cu dma_aux scan_burst select_single
+// stdin, one case per line:  op c P layout hits n kernel_flags shared_vpl scan_nt_stores max_blocks_per_cu dma_aux scan_burst select_single
+//   (kernel_flags: the option as a caller sets it; it goes through kernel_switch_word() as in capi.hip's launch())
 // stdout, one line per case: <family or -1> TAB <launch record line>
+// --switches: the table of switches.hpp instead, one row per line: name TAB option value TAB kernel bit TAB receiver
 #include <cstdio>
+#include <cstring>
 #include <string>
 
 #include "dispatch.hpp"
 
 using namespace mi355;
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "--switches")) {
+        for (const SwitchRow &s : kSwitches) printf("%s\t%u\t0x%x\t%s\n", s.name, s.option, s.kbit, kSwitchReceiverName[s.receiver]);
+        return 0;
+    }
     hipError_t (*const groups[kNumGroups])(const LaunchReq &) = MI355_GROUP_TABLE(launch_group_);
     int op, layout, hits, shared_vpl, nts, max_bpc, dma_aux, burst, single;
     unsigned c, P, flags;
@@ -41,7 +48,7 @@ int main()
         r.scan.nkeys = P;
         r.scan.layout = (uint32_t)layout;
         r.scan.hits = hits ? &dummy : nullptr;
-        r.scan.flags = flags;
+        r.scan.flags = kernel_switch_word(flags, op == kOpSelect);
         r.decomp.n = n;
         const hipError_t e = groups[(c - 1) / 4](r);
         if (e != hipSuccess) {

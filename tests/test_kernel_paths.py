@@ -2,8 +2,8 @@
 arguments) that the call must launch, as mi355_ctx_last_launch reports it.
 
 CPU: every __global__ kernel of csrc/kernels/*.hpp and csrc/extras/*.hpp is the expected kernel of some case; the variant
-axes the launcher picks between are covered; every kernel-side `flags & <const>` test maps (through the shifts in capi.hip)
-to an option bit of the matrix, and every option bit of the matrix has a case.
+axes the launcher picks between are covered; every kernel-side `flags &` test names a switch of csrc/switches.hpp whose
+option value is in the matrix, the table maps option values as the shifts it replaced did, and every option bit of the matrix has a case.
 GPU (-m gpu): each case runs, its launch record matches, and every output byte equals numpy, inside 0xEE guard bytes that
 must stay untouched.  A shared scan also asks mi355_shared_scan_kernel under its options: the family named is the one launched.  A case with an option bit also runs without that bit: the record must change (the launcher really
 took the other path) and the results must not.  The counter-flush cases run on a 4-wave grid (grid_cus = 1,
@@ -35,7 +35,7 @@ LAUNCHER_SET = {0x20000: "short last table attached (shared_linear2_kernel)", 0x
 SHARED_BITS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 8192, 16384, 32768, 131072, 262144, 524288, 1048576, 4194304, 8388608]
 SELECT_BITS = [2048, 4096, 2048 + 4096]
 TIMING_ABLATIONS = {512: "selection: no expansion (wrong ids by construction)", 1024: "selection: no look-back (wrong ids by construction)"}
-UNUSED_BITS = {65536: "kernel bit 0x1000: read nowhere (capi.hip keeps it out of the kernels' word)"}
+UNUSED_BITS = {65536: "kernel bit 0x1000: read nowhere (reserved in csrc/switches.hpp: it stays out of the kernels' word)"}
 
 
 @dataclass(frozen=True)
@@ -320,59 +320,102 @@ def test_every_variant_has_a_case(pattern, set_bits, clear_bits, what):
     assert hits, f"no case covers {what} ({pattern})"
 
 
-def flag_shifts():
-    """the two expressions of capi.hip's launch(): the selection's mask, the shared scans' low mask and high mask"""
-    text = open(os.path.join(CSRC, "capi.hip")).read()
-    m = re.search(r"r\.op == kOpSelect \? \(\(ctx->kernel_flags >> 8\) & (0x[0-9a-f]+)u\) : \(\(ctx->kernel_flags & (0x[0-9a-f]+)u\) \| "
-                  r"\(\(ctx->kernel_flags >> 4\) & (0x[0-9a-f]+)u\)\)", text)
-    assert m, "capi.hip: the kernel_flags shifts changed; update this test's mapping"
-    return tuple(int(g, 16) for g in m.groups())
+def switch_table():
+    """csrc/switches.hpp as tests/cpp/launch_dry_run --switches prints it: [(name, option value, kernel-side bit, receiver)]"""
+    import subprocess
+
+    from test_launch_plan import build_binary
+
+    out = subprocess.run([build_binary(), "--switches"], capture_output=True, text=True, timeout=60, check=True).stdout
+    return [(name, int(opt), int(kbit, 16), recv) for name, opt, kbit, recv in (ln.split("\t") for ln in out.splitlines())]
 
 
-def kernel_flag_tests():
-    """(file, kernel-side bit) for every `flags & <const>` of width_group.hip, shared_plan.hpp and kernels/*.hpp"""
-    out = []
-    for f in [os.path.join(CSRC, "width_group.hip"), os.path.join(CSRC, "shared_plan.hpp")] + sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hpp"))):
-        text = strip_comments(strip_debug_blocks(open(f).read()))
-        for const in re.findall(r"\bflags\s*&\s*(0x[0-9a-fA-F]+|\d+)u?\b", text):
-            v = int(const, 0)
-            out += [(os.path.basename(f), 1 << k) for k in range(32) if v >> k & 1]
-    return out
+def switch_words(options):
+    """[(shared scans' word, selection's word)] of kernel_switch_word() per option value, read from the flags=0x... of the launch
+    record of an equality scan (every launch but the selection's carries the shared scans' word) and of a selection"""
+    from test_launch_plan import dry_run
 
-
-def option_bit_of(fname, kbit):
-    sel_mask, lo_mask, hi_mask = flag_shifts()
-    if fname in ("select.hpp", "select2.hpp"):
-        return kbit << 8 if kbit & sel_mask else None
-    if kbit & lo_mask:
-        return kbit
-    if kbit & hi_mask:
-        return kbit << 4
-    return None
+    recs = dry_run([(op, 9, 1, 0, 1, N_SMALL, v, 0, -1, 0, 18, 0, 0) for v in options for op in (0, 5)])
+    words = [parse_record(text)[0][3] for _, text in recs]
+    return list(zip(words[0::2], words[1::2]))
 
 
 def test_flag_shifts_keep_the_selection_apart():
-    sel_mask, lo_mask, hi_mask = flag_shifts()
-    sel_options = {(1 << b) << 8 for b in range(32) if sel_mask >> b & 1}
-    shared_options = {1 << b for b in range(32) if lo_mask >> b & 1} | {(1 << b) << 4 for b in range(32) if hi_mask >> b & 1}
-    assert not sel_options & shared_options, "an option bit reaches both the shared scans and the selection"
-    assert sel_options == set(SELECT_BITS[:2]) | set(TIMING_ABLATIONS), sorted(sel_options)
-    for b in LAUNCHER_SET:
-        assert not b & hi_mask and not b & lo_mask, f"launcher-set bit {b:#x} reachable from the option"
-    for b in UNUSED_BITS:
-        assert not (b >> 4) & hi_mask, f"unused option bit {b} reaches the kernels"
+    rows = switch_table()
+    assert len({r[0] for r in rows}) == len(rows) and {r[3] for r in rows} == {"shared", "select", "launcher-set", "reserved"}, rows
+    options = {recv: {r[1] for r in rows if r[3] == recv} for recv in ("shared", "select", "launcher-set", "reserved")}
+    kbits = {recv: {r[2] for r in rows if r[3] == recv} for recv in options}
+    assert not options["select"] & options["shared"], "an option bit reaches both the shared scans and the selection"
+    assert options["select"] == set(SELECT_BITS[:2]) | set(TIMING_ABLATIONS) == {512, 1024, 2048, 4096}, sorted(options["select"])
+    assert options["shared"] == set(SHARED_BITS), sorted(options["shared"])
+    assert options["launcher-set"] == {0}, "a launcher-set switch has an option value"
+    assert kbits["launcher-set"] == set(LAUNCHER_SET), kbits["launcher-set"]
+    assert options["reserved"] == set(UNUSED_BITS), options["reserved"]
+    # neither the launcher's own rows (no option value) nor the reserved one give a receiver anything, and no option bit at all
+    # brings about a launcher-set or reserved kernel bit, or one of the other receiver
+    for v, (shared, select) in zip([0] + sorted(UNUSED_BITS), switch_words([0] + sorted(UNUSED_BITS))):
+        assert shared == 0 and select == 0, f"option value {v} reaches the kernels: {shared:#x} / {select:#x}"
+    singles = [1 << b for b in range(32)]
+    for v, (shared, select) in zip(singles, switch_words(singles)):
+        assert not shared & ~sum(kbits["shared"]) and not select & ~sum(kbits["select"]), f"option bit {v}: {shared:#x} / {select:#x}"
+        assert not (shared and select), f"option bit {v} reaches both the shared scans and the selection"
+
+
+# what capi.hip's launch() computed before csrc/switches.hpp held the table (recorded old behaviour): select, everything else
+OLD_SWITCH_WORD = (lambda v: (v >> 8) & 0x1e, lambda v: (v & 0x1ff) | ((v >> 4) & 0xdee00))
+
+
+def test_switch_word_is_what_the_shifts_gave():
+    """the mapping is bitwise, so the 32 single-bit option values cover it"""
+    singles = [1 << b for b in range(32)]
+    for v, (shared, select) in zip(singles, switch_words(singles)):
+        assert select == OLD_SWITCH_WORD[0](v), f"option bit {v}, selection: {select:#x}"
+        assert shared == OLD_SWITCH_WORD[1](v), f"option bit {v}, shared scans: {shared:#x}"
+
+
+FLAGS_AND = r"\bflags\s*&(?!&)"
+
+
+def kernel_flag_tests():
+    """(file, switch name) for every `flags & <name>` / `flags & (<name> | <name>)` of width_group.hip, shared_plan.hpp and
+    kernels/*.hpp; whatever else follows a `flags &` fails here"""
+    out = []
+    for f in [os.path.join(CSRC, "width_group.hip"), os.path.join(CSRC, "shared_plan.hpp")] + sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hpp"))):
+        text = strip_comments(strip_debug_blocks(open(f).read()))
+        assert not re.search(FLAGS_AND + r"[\s(]*(0x[0-9a-fA-F]+|\d)", text), f"{os.path.basename(f)}: a numeric literal next to `flags &`"
+        found = re.findall(FLAGS_AND + r"\s*(?:\(([^()]*)\)|([A-Za-z_]\w*))", text)
+        assert len(found) == len(re.findall(FLAGS_AND, text)), f"{os.path.basename(f)}: a `flags &` without a switch name behind it"
+        for group, one in found:
+            out += [(os.path.basename(f), name.strip()) for name in (group.split("|") if group else [one])]
+    return out
 
 
 def test_kernel_flag_tests_are_in_the_matrix():
     tests = kernel_flag_tests()
     assert len(tests) >= 20, tests  # the parse found the launcher's switches
+    table = {name: (opt, kbit, recv) for name, opt, kbit, recv in switch_table()}
     documented = set(SHARED_BITS) | set(SELECT_BITS) | set(TIMING_ABLATIONS)
-    for fname, kbit in tests:
-        if fname not in ("select.hpp", "select2.hpp") and kbit in LAUNCHER_SET:
-            continue
-        opt = option_bit_of(fname, kbit)
-        assert opt is not None, f"{fname}: flags bit {kbit:#x} is reachable from no option bit (nor set by the launcher)"
-        assert opt in documented, f"{fname}: flags bit {kbit:#x} = option bit {opt}: not in the option-bit matrix"
+    for fname, name in tests:
+        assert name in table, f"{fname}: `flags & {name}`: not a switch of csrc/switches.hpp"
+        opt, kbit, recv = table[name]
+        if fname in ("select.hpp", "select2.hpp"):
+            assert recv == "select", f"{fname}: {name} is a switch of receiver {recv}"
+        else:
+            assert recv in ("shared", "launcher-set"), f"{fname}: {name} is a switch of receiver {recv}"
+            if recv == "launcher-set":
+                assert kbit in LAUNCHER_SET, f"{fname}: {name} = {kbit:#x}"
+                continue
+        assert opt in documented, f"{fname}: {name} = option bit {opt}: not in the option-bit matrix"
+
+
+def test_design_lists_every_switch():
+    """DESIGN.md's "A/B switches" section has every row of the table, name and option value on one line"""
+    text = open(os.path.join(ROOT, "DESIGN.md")).read()
+    start = text.index("**A/B switches.**")
+    section = text[start:text.index("\n## 9.", start)].splitlines()
+    for name, opt, kbit, recv in switch_table():
+        cell = str(opt) if opt else "—"
+        assert any(re.search(rf"\|\s*`{name}`\s*\|\s*{cell}\s*\|\s*{recv}\s*\|", ln) for ln in section), f"DESIGN.md section 8: no row for {name} ({cell}, {recv})"
 
 
 def test_every_option_bit_has_a_case():

@@ -15,7 +15,7 @@ import glob
 import os
 import subprocess
 
-from test_kernel_paths import CASES, CSRC, N_SMALL, family_of, flag_shifts, label_matches, parse_record
+from test_kernel_paths import CASES, CSRC, N_SMALL, family_of, label_matches, parse_record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "launch_dry_run.cpp")
@@ -42,7 +42,7 @@ def build_binary():
         build.build()
     objs = group_objects()
     assert len(objs) == 8, objs
-    newest = max(os.path.getmtime(f) for f in [SRC, os.path.join(CSRC, "dispatch.hpp")] + objs)
+    newest = max(os.path.getmtime(f) for f in [SRC, os.path.join(CSRC, "dispatch.hpp"), os.path.join(CSRC, "switches.hpp")] + objs)
     if not os.path.exists(BIN) or os.path.getmtime(BIN) < newest:
         os.makedirs(os.path.dirname(BIN), exist_ok=True)
         obj = BIN + ".o"  # (compiled on its own: hipcc would read the group objects as HIP sources next to a .cpp)
@@ -52,7 +52,7 @@ def build_binary():
 
 
 def dry_run(rows):
-    """rows of (op, c, P, layout, hits, n, flags, shared_vpl, scan_nt_stores, max_blocks_per_cu, dma_aux, scan_burst, select_single)
+    """rows of (op, c, P, layout, hits, n, kernel_flags, shared_vpl, scan_nt_stores, max_blocks_per_cu, dma_aux, scan_burst, select_single)
     -> [(family index or -1, launch record text)]"""
     text = "".join(" ".join(str(int(v)) for v in row) + "\n" for row in rows)
     res = subprocess.run([build_binary()], input=text, capture_output=True, text=True, timeout=300)
@@ -62,17 +62,10 @@ def dry_run(rows):
     return [(int(fam), rec) for fam, rec in out]
 
 
-def kernel_side_flags(case):
-    """the option "kernel_flags" as the kernels receive it: the two expressions of capi.hip's launch()"""
-    sel_mask, lo_mask, hi_mask = flag_shifts()
-    kf = case.opt("kernel_flags")
-    return (kf >> 8) & sel_mask if case.op == "select" else (kf & lo_mask) | ((kf >> 4) & hi_mask)
-
-
 def test_kernel_path_cases_without_a_gpu():
     cases = [c for c in CASES if c.op in WIDTH_OPS]
     assert len(cases) >= 90 and {c.op for c in cases} == set(WIDTH_OPS), len(cases)
-    rows = [(WIDTH_OPS[c.op], c.c, c.P, c.layout, c.hits, c.n, kernel_side_flags(c), c.opt("shared_vpl"), c.opt("scan_nt_stores", -1),
+    rows = [(WIDTH_OPS[c.op], c.c, c.P, c.layout, c.hits, c.n, c.opt("kernel_flags"), c.opt("shared_vpl"), c.opt("scan_nt_stores", -1),
              c.opt("max_blocks_per_cu"), c.opt("dma_aux", 18), c.opt("scan_burst"), c.opt("select_kernel") == 1) for c in cases]
     for case, (fam, text) in zip(cases, dry_run(rows)):
         rec = parse_record(text)

@@ -6,7 +6,8 @@ ABI (include/mi355_scan.h, shared_simd_scan_amd/libmi355scan.so).  See DESIGN.md
 """
 from ._capi import Mi355Error, lib  # noqa: F401
 from .engine import (PackedColumn, ScanEngine, clamp_diff, compressed_buffer_size, decompression_output_buffer_size,  # noqa: F401
-                     kernel_name, scan_output_buffer_size, semi_join_kernel, shared_where_kernel, tile_values)
+                     kernel_name, lookup_kernel, scan_output_buffer_size, semi_join_kernel, shared_where_kernel, tile_values)
 
 __all__ = ["Mi355Error", "PackedColumn", "ScanEngine", "compressed_buffer_size", "decompression_output_buffer_size",
-           "scan_output_buffer_size", "kernel_name", "shared_where_kernel", "tile_values", "lib", "clamp_diff", "semi_join_kernel"]
+           "scan_output_buffer_size", "kernel_name", "shared_where_kernel", "tile_values", "lib", "clamp_diff", "semi_join_kernel",
+           "lookup_kernel"]

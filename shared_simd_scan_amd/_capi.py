@@ -1,4 +1,4 @@
-"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h and include/mi355_semijoin.h.  No compute happens in Python; a missing library is an error."""
+"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h, include/mi355_semijoin.h and include/mi355_lookup.h.  No compute happens in Python; a missing library is an error."""
 from __future__ import annotations
 
 import ctypes as C
@@ -99,6 +99,12 @@ SEMIJOIN_SYMBOLS = [
     ("mi355_semijoin_kernel", C.c_char_p, [C.c_uint, _u64]),
 ]
 
+# every symbol include/mi355_lookup.h declares (a column mapped through a device-resident packed table): bound by lib() as well
+LOOKUP_SYMBOLS = [
+    ("mi355_lookup_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _u64, C.c_uint, C.c_uint32, _vp]),
+    ("mi355_lookup_kernel", C.c_char_p, [C.c_uint, _u64, C.c_uint]),
+]
+
 
 class Predicate(C.Structure):
     """mi355_predicate: one comparison `v OP a [, b]` of a shared where-scan"""
@@ -118,7 +124,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the HIP extension is not built (run `python -m shared_simd_scan_amd.build`). "
                 "There is no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS:
+        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS + LOOKUP_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export what the header declares
             fn.restype = res
             fn.argtypes = args

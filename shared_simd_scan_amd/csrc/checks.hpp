@@ -73,6 +73,13 @@ inline int check_some_output(const void *bitmap_dev, const void *hits_dev)
 
 inline size_t bitmap_bytes(uint64_t n) { return (size_t)((n + 7) / 8); }
 
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (an output that overlaps an input a kernel reads while it writes)
+inline bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a_bytes && b_bytes && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
 // the per-predicate layout puts bitmap k at out_dev + k * stride_bytes: every one of them 16-byte aligned and long enough
 inline int check_stride(int layout, uint64_t stride_bytes, uint64_t n)
 {

@@ -28,6 +28,28 @@ template <auto Kernel> void allow_dynamic_lds(int max_bytes, int device)
     }
 }
 
+constexpr size_t kCuLdsBytes = 160 * 1024; // LDS of a CU
+
+// Blocks per CU of a kernel with `lds` bytes of dynamic LDS: what registers and LDS admit, at most four (one LDS or L2 lookup per
+// value: further waves per SIMD hide the lookups' latency; the rule of group_aggregate.hip).  Shared by the kernels that size a
+// lookup table in dynamic LDS to their arguments: the semi-join (its set) and lookup (its table).  The occupancy query is asked once
+// per kernel and device, without dynamic LDS: that is the registers' and the static LDS's limit.  The table's share is arithmetic
+// on top -- blocks of `fixed_lds` + `lds` bytes in a CU's 160 KiB -- so a caller that alternates between table sizes, or captures a
+// graph, never repeats the query.  (An answer one too high would only leave a block of the persistent grid queued.)
+template <auto Kernel> int table_bpc(size_t lds, size_t fixed_lds, int device)
+{
+    static std::atomic<signed char> by_regs[64]; // 0 = not asked on this device yet
+    std::atomic<signed char> &slot = by_regs[device & 63];
+    int bpc = slot.load(std::memory_order_relaxed);
+    if (bpc == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, Kernel, kBlockThreads, 0) != hipSuccess || bpc < 1) bpc = 1;
+        if (bpc > 4) bpc = 4;
+        slot.store((signed char)bpc, std::memory_order_relaxed);
+    }
+    const int by_lds = (int)(kCuLdsBytes / (fixed_lds + lds));
+    return by_lds < 1 ? 1 : (by_lds < bpc ? by_lds : bpc);
+}
+
 // option "max_blocks_per_cu" (0 = no cap) on top of what a kernel admits
 inline int cap_bpc(int bpc, int max_blocks_per_cu) { return (max_blocks_per_cu > 0 && max_blocks_per_cu < bpc) ? max_blocks_per_cu : bpc; }
 

@@ -3,8 +3,6 @@
 // entry points nor the width groups rebuild with it.
 #include "../ctx.hpp"
 
-#include <atomic>
-
 #include "../../../include/mi355_semijoin.h"
 #include "../checks.hpp"
 #include "../dispatch.hpp"
@@ -29,29 +27,10 @@ struct SemiLaunch {
     std::string *record;
 };
 
-// Blocks per CU of a kernel with `lds` bytes of dynamic LDS: what registers and LDS admit, at most four (one LDS or L2 lookup per
-// value: further waves per SIMD hide the lookups' latency; the rule of group_aggregate.hip).  The occupancy query is asked once
-// per kernel and device, without dynamic LDS: that is the registers' and the static LDS's limit.  The set's share is arithmetic
-// on top -- blocks of `fixed_lds` + `lds` bytes in a CU's 160 KiB -- so a caller that alternates between set sizes, or captures a
-// graph, never repeats the query.  (An answer one too high would only leave a block of the persistent grid queued.)
-template <auto Kernel> int semijoin_bpc(size_t lds, size_t fixed_lds, int device)
-{
-    static std::atomic<signed char> by_regs[64]; // 0 = not asked on this device yet
-    std::atomic<signed char> &slot = by_regs[device & 63];
-    int bpc = slot.load(std::memory_order_relaxed);
-    if (bpc == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, Kernel, kBlockThreads, 0) != hipSuccess || bpc < 1) bpc = 1;
-        if (bpc > 4) bpc = 4;
-        slot.store((signed char)bpc, std::memory_order_relaxed);
-    }
-    const int by_lds = (int)(kSemiCuLds / (fixed_lds + lds));
-    return by_lds < 1 ? 1 : (by_lds < bpc ? by_lds : bpc);
-}
-
 template <auto Kernel> void launch_tier(const SemiLaunch &r, uint64_t ntiles, size_t lds, size_t fixed_lds, int max_dyn)
 {
     if (max_dyn > 0) allow_dynamic_lds<Kernel>(max_dyn, r.device);
-    const unsigned grid = grid_for(ntiles, cap_bpc(semijoin_bpc<Kernel>(lds, fixed_lds, r.device), r.max_blocks_per_cu), r.num_cus);
+    const unsigned grid = grid_for(ntiles, cap_bpc(table_bpc<Kernel>(lds, fixed_lds, r.device), r.max_blocks_per_cu), r.num_cus);
     MI355_LAUNCH(r.record, 0, Kernel, dim3(grid), dim3(kBlockThreads), lds, r.stream, r.k);
 }
 
@@ -72,12 +51,6 @@ template <int C> hipError_t launch_semijoin(const SemiLaunch &r)
             return hipErrorInvalidValue; // semijoin_in_lds() is true below kSemiGlobalMinBits
     }
     return hipGetLastError();
-}
-
-bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a_bytes && b_bytes && pa < pb + b_bytes && pb < pa + a_bytes;
 }
 
 } // namespace

@@ -127,6 +127,17 @@ def semi_join_kernel(c: int, set_bits: int) -> str:
     return s.decode()
 
 
+def lookup_kernel(c: int, table_rows: int, ct: int) -> str:
+    """kernel family ScanEngine.lookup launches for a column of width c and a table of table_rows values of width ct
+    (mi355_lookup_kernel; arithmetic only, needs no device): 'lookup_lds_kernel' | 'lookup_global_kernel'"""
+    if not 0 <= int(table_rows) <= 1 << 32:
+        raise ValueError((c, table_rows, ct))
+    s = lib().mi355_lookup_kernel(c, int(table_rows), ct)
+    if s is None:
+        raise ValueError((c, table_rows, ct))
+    return s.decode()
+
+
 class PackedColumn:
     """A bit-packed column resident in HBM: `n` values of `c` bits, reference stream format."""
 
@@ -370,6 +381,22 @@ class ScanEngine:
                                        set_bits, 1 if negate else 0, and_mask.data_ptr() if and_mask is not None else None,
                                        None if count_only else bitmap.data_ptr(), hits.data_ptr() if want_hits else None))
         return (None if count_only else bitmap), hits
+
+    def lookup(self, col: PackedColumn, table: PackedColumn, miss: int = 0, out: Optional[torch.Tensor] = None) -> PackedColumn:
+        """out[i] = table[value_i] if value_i < table.n else miss, as a packed column of col.n values of table.c bits: for every
+        fact row the attribute of the dimension row its key points at (then `group_aggregate` by it, or any scan over it), or
+        a dictionary re-code.  `out`: a uint8 device tensor of at least compressed_buffer_size(table.c, col.n) bytes that
+        overlaps neither input (allocated when None).  Capturable into a graph: the table is read at every replay."""
+        miss = int(miss)
+        if not 0 <= miss < 1 << table.c:
+            raise ValueError(f"miss {miss} is no value of {table.c} bits")  # (ctypes would wrap it silently)
+        if out is None:
+            out = torch.empty(compressed_buffer_size(table.c, col.n), dtype=torch.uint8, device=self._dev)
+        else:
+            assert out.dtype == torch.uint8 and out.numel() >= (col.n * table.c + 7) // 8
+        check(lib().mi355_lookup_dev(self._ctx, col.data.data_ptr(), col.n, col.c, table.data.data_ptr() if table.n else None, table.n,
+                                     table.c, miss, out.data_ptr()))
+        return PackedColumn(out, col.n, table.c)
 
     def bitmap_combine(self, op: str, a: torch.Tensor, b: torch.Tensor, n: int, out: Optional[torch.Tensor] = None):
         if out is None:

@@ -143,8 +143,7 @@ int launch_columns(mi355_ctx *ctx, ColumnsReq &r)
     r.k.s.scratch = ctx->kernel_scratch;
     // bitmap stores as scan2_kernel's: write-through below 768 MiB of bitmap, non-temporal beyond; "scan_nt_stores" overrides
     r.k.nts = (uint32_t)one_pass_store_policy(r.k.s.n / 8, ctx->scan_nt_stores);
-    ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
-    ctx->llc_last_d = -1;
+    llc_forget(ctx);
     hipError_t e = kColumnsGroups[(r.l.c - 1) / 4](r);
     if (e != hipSuccess) return fail(MI355_E_HIP, "kernel launch (column scan, c1=%u c2=%u): %s", r.l.c, r.k.c2, hipGetErrorString(e));
     return MI355_OK;

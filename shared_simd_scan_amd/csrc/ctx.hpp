@@ -1,5 +1,6 @@
 // ctx.hpp -- the context object behind include/mi355_scan.h and what every host-side translation unit of libmi355scan.so
-// shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip, groupby/group_aggregate.hip):
+// shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip, groupby/group_aggregate.hip,
+// semijoin/semijoin.hip, lookup/lookup.hip):
 // error reporting, the entry prologue, the context's buffers.
 #pragma once
 
@@ -154,5 +155,17 @@ int upload_list(mi355_ctx *ctx, const void *src, size_t elem_bytes, unsigned P, 
 
 // CUs the persistent grids are sized for (option "grid_cus")
 inline int grid_cus(const mi355_ctx *ctx) { return ctx->grid_cus > 0 ? ctx->grid_cus : ctx->num_cus; }
+
+// What a launcher outside the width groups (groupby/, semijoin/, lookup/) takes from its context; the groups' LaunchReq has the
+// same five among its fields (capi.hip fill_common).
+struct LaunchEnv {
+    hipStream_t stream;
+    int device, num_cus, max_blocks_per_cu; // num_cus: grid_cus(); max_blocks_per_cu: 0 = no cap
+    std::string *record;                    // mi355_ctx_last_launch
+};
+inline LaunchEnv launch_env(mi355_ctx *ctx) { return {ctx->stream, ctx->device, grid_cus(ctx), ctx->max_blocks_per_cu, &ctx->last_launch}; }
+
+// another kernel's traffic went through the cache: the next eq / range scan is no repeat, and no divisor was chosen
+inline void llc_forget(mi355_ctx *ctx) { ctx->llc_prev[0] = nullptr, ctx->llc_last_d = -1; }
 
 } // namespace mi355

@@ -13,6 +13,16 @@
 
 using namespace mi355;
 
+namespace {
+// `blocks`, capped at per_cu for each of the CUs the grids are sized for; at_least_one: no blocks still launch one
+unsigned capped_grid(mi355_ctx *ctx, uint64_t blocks, int per_cu, bool at_least_one)
+{
+    const uint64_t cap = (uint64_t)grid_cus(ctx) * per_cu;
+    if (at_least_one && blocks == 0) blocks = 1;
+    return (unsigned)(blocks < cap ? blocks : cap);
+}
+} // namespace
+
 extern "C" {
 
 /* ---- pack / generate ---- */
@@ -31,16 +41,12 @@ static int pack_launch(mi355_ctx *ctx, int src, const void *values_dev, uint64_t
     a.out = (uint32_t *)packed_dev;
     a.out_dwords = mi355_compressed_buffer_size(c, n) / 4; // payload + pad, whole dwords
     a.c = c;
-    uint64_t blocks = (a.out_dwords + 255) / 256;
-    uint64_t cap = (uint64_t)grid_cus(ctx) * 8;
-    unsigned grid = (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
+    const unsigned grid = capped_grid(ctx, (a.out_dwords + 255) / 256, 8, true);
     std::string *const rec = &ctx->last_launch;
     switch (src) {
 #define PACK_BY_WIDTH(SRC)                                                                                          \
     do { /* values per output dword: at most floor(31/c) + 2; one block per 8192-value tile, 4 resident per CU */  \
-        uint64_t tiles = (n + kPackTile - 1) / kPackTile;                                                           \
-        uint64_t tcap = (uint64_t)grid_cus(ctx) * 4;                                                                \
-        unsigned tgrid = (unsigned)(tiles < tcap ? (tiles ? tiles : 1) : tcap);                                     \
+        const unsigned tgrid = capped_grid(ctx, (n + kPackTile - 1) / kPackTile, 4, true);                         \
         if (c >= 16) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 3>), dim3(tgrid), dim3(256), 0, ctx->stream, a);    \
         else if (c >= 8) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 5>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
         else if (c >= 4) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 9>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
@@ -127,9 +133,7 @@ static int bitmap_launch(mi355_ctx *ctx, int op, const void *a, const void *b, v
     g.nbytes = bitmap_bytes(n);
     // partial counts go to the (all-zero) hit-count replicas of the context scratch, then to count_dev
     g.count = count_dev ? ctx->kernel_scratch : nullptr;
-    uint64_t blocks = (g.nbytes / 16 + 255) / 256;
-    const uint64_t cap = (uint64_t)grid_cus(ctx) * 4;
-    unsigned grid = (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
+    const unsigned grid = capped_grid(ctx, (g.nbytes / 16 + 255) / 256, 4, true);
     std::string *const rec = &ctx->last_launch;
     switch (op) {
     case kBitAnd: MI355_LAUNCH(rec, 0, bitmap_kernel<kBitAnd>, dim3(grid), dim3(256), 0, ctx->stream, g); break;
@@ -182,8 +186,7 @@ int mi355_bitmap_to_rowids_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t 
     g.chunk_counts = ctx->rowid_ws;
     g.rowids = rowids_dev;
     g.capacity = capacity;
-    uint64_t blocks = (g.nchunks + 3) / 4;
-    unsigned grid = (unsigned)(blocks < (uint64_t)grid_cus(ctx) * 8 ? blocks : (uint64_t)grid_cus(ctx) * 8);
+    const unsigned grid = capped_grid(ctx, (g.nchunks + 3) / 4, 8, false);
     std::string *const rec = &ctx->last_launch;
     MI355_LAUNCH(rec, 0, rowid_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
     MI355_LAUNCH(rec, 0, rowid_scan_kernel, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, g);
@@ -213,8 +216,7 @@ int mi355_gather_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
     g.capacity = capacity;
     g.out = out_dev;
     // the grid is sized for `capacity` (the count is only known on the device); idle blocks leave at once
-    const uint64_t blocks = (capacity + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < (uint64_t)grid_cus(ctx) * 16 ? blocks : (uint64_t)grid_cus(ctx) * 16);
+    const unsigned grid = capped_grid(ctx, (capacity + 255) / 256, 16, false);
     MI355_LAUNCH(&ctx->last_launch, 0, gather_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     return MI355_OK;

@@ -107,7 +107,7 @@ template <int C> inline void launch_histogram(const HistArgs &a, int num_cus, hi
     using G = ScanGeom<C, VPL>;
     const uint64_t ntiles = (a.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
     // two blocks per CU while tiles + counters of two blocks fit in the CU's 160 KiB (the LDS atomics want the second wave per SIMD)
-    const bool two = 2 * (4 * (size_t)G::LDS_BYTES + (4u << C)) + 1024 <= 160 * 1024;
+    const bool two = 2 * (4 * (size_t)G::LDS_BYTES + (4u << C)) + 1024 <= kCuLdsBytes;
     const uint64_t blocks_wanted = (uint64_t)num_cus * (two ? 2 : 1);
     const uint64_t blocks_needed = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const unsigned grid = (unsigned)(blocks_needed < blocks_wanted ? (blocks_needed ? blocks_needed : 1) : blocks_wanted);

@@ -1,6 +1,6 @@
 // group_aggregate.hip -- implementation of include/mi355_groupby.h: argument checks and the launch of
 // group_aggregate_kernel (groupby/group_aggregate.hpp) by key width.  Its own translation unit: neither the other entry points nor the
-// width groups rebuild with it.
+// width groups rebuild with it.  What it takes from the context is a LaunchEnv (ctx.hpp), as in semijoin/ and lookup/.
 #include "../ctx.hpp"
 
 #include <atomic>
@@ -20,10 +20,14 @@ static_assert(kGroupMaxBits == MI355_GROUP_MAX_KEY_BITS, "the header's limit is 
 struct GroupLaunch {
     GroupArgs k;
     unsigned ck;
-    hipStream_t stream;
-    int device, num_cus, max_blocks_per_cu;
-    std::string *record;
+    LaunchEnv env;
 };
+
+// every group's slot to its neutral element: all an empty column takes, and what group_aggregate_kernel starts from
+void launch_init(const LaunchEnv &env, unsigned long long *out, unsigned ck)
+{
+    MI355_LAUNCH(env.record, 0, group_aggregate_init_kernel, dim3(((1u << ck) + 255u) / 256u), dim3(256), 0, env.stream, out, 1u << ck);
+}
 
 template <int CK> hipError_t launch_group(const GroupLaunch &r)
 {
@@ -31,7 +35,7 @@ template <int CK> hipError_t launch_group(const GroupLaunch &r)
     const uint32_t cv = r.k.cv;
     const uint64_t ntiles = (r.k.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
     const size_t lds = group_block_lds<CK>(cv);
-    allow_dynamic_lds<group_aggregate_kernel<CK>>((int)group_block_lds<CK>(32), r.device);
+    allow_dynamic_lds<group_aggregate_kernel<CK>>((int)group_block_lds<CK>(32), r.env.device);
     // Blocks per CU: small tiles, LDS reads and atomics all through a tile -- as many blocks as LDS and registers admit, up to
     // 4 waves per SIMD (the rule of scan_columns_kernel's run-time-width form).  The query depends on the dynamic LDS, i.e.
     // on cv: asked once per value width.
@@ -42,12 +46,12 @@ template <int CK> hipError_t launch_group(const GroupLaunch &r)
         if (bpc > 4) bpc = 4;
         bpc_of[cv].store(bpc, std::memory_order_relaxed);
     }
-    unsigned grid = grid_for(ntiles, cap_bpc(bpc, r.max_blocks_per_cu), r.num_cus);
+    unsigned grid = grid_for(ntiles, cap_bpc(bpc, r.env.max_blocks_per_cu), r.env.num_cus);
     // a block's counts are 32-bit words in LDS: no block may see 2^32 rows (a grid beyond what is resident simply queues)
     const uint64_t min_grid = (r.k.n >> 31) + 1;
     if (grid < min_grid) grid = (unsigned)min_grid;
-    MI355_LAUNCH(r.record, 0, group_aggregate_init_kernel, dim3(((1u << CK) + 255u) / 256u), dim3(256), 0, r.stream, r.k.out, 1u << CK);
-    MI355_LAUNCH(r.record, 0, (group_aggregate_kernel<CK>), dim3(grid), dim3(kBlockThreads), lds, r.stream, r.k);
+    launch_init(r.env, r.k.out, CK);
+    MI355_LAUNCH(r.env.record, 0, (group_aggregate_kernel<CK>), dim3(grid), dim3(kBlockThreads), lds, r.env.stream, r.k);
     return hipGetLastError();
 }
 
@@ -73,13 +77,9 @@ int mi355_group_aggregate_dev(mi355_ctx *ctx, const void *keys_dev, unsigned ck,
     r.k.out = (unsigned long long *)out_dev;
     r.k.cv = cv;
     r.ck = ck;
-    r.stream = ctx->stream;
-    r.device = ctx->device;
-    r.num_cus = grid_cus(ctx);
-    r.max_blocks_per_cu = ctx->max_blocks_per_cu;
-    r.record = &ctx->last_launch;
+    r.env = launch_env(ctx);
     if (n == 0) {
-        MI355_LAUNCH(r.record, 0, group_aggregate_init_kernel, dim3(((1u << ck) + 255u) / 256u), dim3(256), 0, r.stream, r.k.out, 1u << ck);
+        launch_init(r.env, r.k.out, ck);
         HIP_TRY(hipGetLastError());
         return MI355_OK;
     }

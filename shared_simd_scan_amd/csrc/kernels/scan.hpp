@@ -85,7 +85,7 @@ template <int C, int VPL, int K> constexpr int burst_occ()
     using G = ScanGeom<C, VPL>;
     constexpr int mask_bytes = (K * G::BITMAP_BYTES + 1023) / 1024 * 1024;
     constexpr int table = narrow_k<C>() ? (1 << (narrow_k<C>() * C)) : 16;
-    constexpr int lds = (160 * 1024) / (4 * (G::LDS_BYTES + mask_bytes) + table + 64);
+    constexpr int lds = kCuLdsBytes / (4 * (G::LDS_BYTES + mask_bytes) + table + 64);
     constexpr int cap = narrow_k<C>() ? 4 : 8;
     return lds > cap ? cap : (lds < 1 ? 1 : lds);
 }

@@ -37,7 +37,7 @@ constexpr int kSel2Window = 4; // state words per lane and poll of the block's l
 // next to the tiles, the parked chunks and the narrow widths' predicate table (12 expanders x 2 bytes x this)
 constexpr int sel2_stage_ids(int fixed_lds_bytes)
 {
-    return fixed_lds_bytes + (kSel2Waves - kSel2Decoders) * 2 * 2048 + 2048 <= 160 * 1024 ? 2048 : 1024;
+    return fixed_lds_bytes + (kSel2Waves - kSel2Decoders) * 2 * 2048 + 2048 <= kCuLdsBytes ? 2048 : 1024;
 }
 
 template <int C, int MODE, int VPL>

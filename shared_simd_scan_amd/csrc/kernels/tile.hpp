@@ -16,7 +16,10 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlockThreads = kWavesPerBlock * 64;
+constexpr int kCuLdsBytes = 160 * 1024; // LDS of a CU: the one place that says so
 constexpr int kMaxKeysPerPass = 8;
+// what a value of width c can reach of a set or table of `count` entries: min(count, 2^c)
+constexpr uint64_t value_reach(unsigned c, uint64_t count) { return (c < 32 && count > (1ull << c)) ? (1ull << c) : count; }
 constexpr int kMaxKeys = 1024;      // what the reference's linear_simple tops out at (src/simd_scan_shared_linear.cpp:78)
 
 // ---- tile geometry of the scan kernels -----------------------------------------------------
@@ -35,7 +38,7 @@ template <int C, int VPL> struct ScanGeom {
     static constexpr int BITMAP_BYTES = TILE_VALUES / 8;
     // waves per SIMD the LDS footprint admits (160 KiB per CU, 4 waves per block), capped at 8:
     // the register allocator is told to aim for that
-    static constexpr int OCC_LDS = (160 * 1024) / (4 * LDS_BYTES + 64); // +64: the block's ticket word
+    static constexpr int OCC_LDS = kCuLdsBytes / (4 * LDS_BYTES + 64); // +64: the block's ticket word
     static constexpr int OCC = OCC_LDS >= 8 ? 8 : (OCC_LDS < 1 ? 1 : OCC_LDS);
 };
 
@@ -52,7 +55,7 @@ template <int C, int VPL, int MODE> constexpr int scan_occ()
     if (MODE != 2 && C <= 7) {
         // table-lookup decode (narrow_k): many lookups in flight, the predicate table (<= 16 KiB) sits next to the
         // tiles, and the launcher runs 1-2 blocks per CU anyway
-        const int with_table = (160 * 1024) / (4 * ScanGeom<C, VPL>::LDS_BYTES + (1 << (narrow_k<C>() * C)) + 64);
+        const int with_table = kCuLdsBytes / (4 * ScanGeom<C, VPL>::LDS_BYTES + (1 << (narrow_k<C>() * C)) + 64);
         return with_table > 4 ? 4 : (with_table < 1 ? 1 : with_table);
     }
     return MODE == 2 ? (lds > 4 ? 4 : lds) : lds;

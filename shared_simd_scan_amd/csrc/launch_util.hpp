@@ -1,5 +1,6 @@
-// launch_util.hpp -- the host-side launch helpers that capi.hip and the three group translation units (width_group.hip,
-// predicates/where_group.hip, predicates/columns_group.hip) share: one copy of each.  No device code.
+// launch_util.hpp -- the host-side launch helpers that the translation units with a launcher share, one copy of each: capi.hip,
+// extras.hip, the three group units (width_group.hip, predicates/where_group.hip, predicates/columns_group.hip) and the feature
+// units (groupby/group_aggregate.hip, semijoin/semijoin.hip, lookup/lookup.hip).  No device code.
 #pragma once
 
 #include <atomic>
@@ -27,8 +28,6 @@ template <auto Kernel> void allow_dynamic_lds(int max_bytes, int device)
         done.fetch_or(bit, std::memory_order_release);
     }
 }
-
-constexpr size_t kCuLdsBytes = 160 * 1024; // LDS of a CU
 
 // Blocks per CU of a kernel with `lds` bytes of dynamic LDS: what registers and LDS admit, at most four (one LDS or L2 lookup per
 // value: further waves per SIMD hide the lookups' latency; the rule of group_aggregate.hip).  Shared by the kernels that size a
@@ -64,6 +63,17 @@ inline int scan_want_bpc(int tile_bytes, int max_blocks_per_cu)
     if (want < 1) want = 1;
     if (want > 4) want = 4; // c = 1, 2 (1-2 KiB tiles): four blocks per CU beat eight by 20 % / 6 % (launches back to back)
     return want;
+}
+
+// One tier of a kernel with a table in LDS, launched on a persistent grid over `ntiles` wave tiles: `lds` bytes of dynamic LDS next
+// to `fixed_lds` of static, blocks per CU by table_bpc.  max_dyn > 0: the most dynamic LDS the kernel is ever given (raised once).
+// Env: LaunchEnv (ctx.hpp, which the group units do not see).
+template <auto Kernel, typename Env, typename Args>
+void launch_tier(const Env &env, const Args &k, uint64_t ntiles, size_t lds, size_t fixed_lds, int max_dyn)
+{
+    if (max_dyn > 0) allow_dynamic_lds<Kernel>(max_dyn, env.device);
+    const unsigned grid = grid_for(ntiles, cap_bpc(table_bpc<Kernel>(lds, fixed_lds, env.device), env.max_blocks_per_cu), env.num_cus);
+    MI355_LAUNCH(env.record, 0, Kernel, dim3(grid), dim3(kBlockThreads), lds, env.stream, k);
 }
 
 // ---- store policies: `scan_nt_stores` is the option (-1 = by size), `out_bytes` what the launch writes ------------------

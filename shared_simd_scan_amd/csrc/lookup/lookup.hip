@@ -1,6 +1,7 @@
 // lookup.hip -- implementation of include/mi355_lookup.h: argument checks, the choice between the two tiers and the launch of
 // lookup_lds_kernel / lookup_global_kernel (lookup/lookup.hpp) by output width.  Its own translation unit: neither the other
-// entry points nor the width groups rebuild with it.
+// entry points nor the width groups rebuild with it.  The launch itself is launch_tier (launch_util.hpp) on a LaunchEnv (ctx.hpp),
+// shared with semijoin/.
 #include "../ctx.hpp"
 
 #include "../../../include/mi355_lookup.h"
@@ -14,33 +15,24 @@ using namespace mi355;
 namespace {
 
 static_assert(kLookupLdsMaxBytes == MI355_LOOKUP_LDS_MAX_BYTES, "the header's limit is the kernels'");
-static_assert(kLookupCuLds == kCuLdsBytes, "one CU, one LDS");
 
 constexpr uint64_t kLookupMaxTableRows = 1ull << 32;
 
 struct LookupLaunch {
     LookupArgs k;
     bool in_lds;
-    hipStream_t stream;
-    int device, num_cus, max_blocks_per_cu;
-    std::string *record;
+    LaunchEnv env;
 };
 
-// all of a block's LDS is dynamic (`lds`: the waves' images, and the table in the LDS tier); blocks per CU: table_bpc
-template <auto Kernel> void launch_tier(const LookupLaunch &r, size_t lds)
-{
-    allow_dynamic_lds<Kernel>((int)(lookup_images_lds(32) + kLookupLdsMaxBytes), r.device);
-    const uint64_t ntiles = (r.k.n + kLookupTileRows - 1) / kLookupTileRows;
-    const unsigned grid = grid_for(ntiles, cap_bpc(table_bpc<Kernel>(lds, 0, r.device), r.max_blocks_per_cu), r.num_cus);
-    MI355_LAUNCH(r.record, 0, Kernel, dim3(grid), dim3(kBlockThreads), lds, r.stream, r.k);
-}
-
+// all of a block's LDS is dynamic: the waves' images, and the table in the LDS tier
 template <int CT> hipError_t launch_lookup(const LookupLaunch &r)
 {
+    const uint64_t ntiles = (r.k.n + kLookupTileRows - 1) / kLookupTileRows;
+    const int max_dyn = (int)(lookup_images_lds(32) + kLookupLdsMaxBytes);
     if (r.in_lds)
-        launch_tier<lookup_lds_kernel<CT>>(r, lookup_images_lds(r.k.c) + lookup_table_lds(r.k.reach, CT));
+        launch_tier<lookup_lds_kernel<CT>>(r.env, r.k, ntiles, lookup_images_lds(r.k.c) + lookup_table_lds(r.k.reach, CT), 0, max_dyn);
     else
-        launch_tier<lookup_global_kernel<CT>>(r, lookup_images_lds(r.k.c));
+        launch_tier<lookup_global_kernel<CT>>(r.env, r.k, ntiles, lookup_images_lds(r.k.c), 0, max_dyn);
     return hipGetLastError();
 }
 
@@ -74,7 +66,7 @@ int mi355_lookup_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
         return fail(MI355_E_INVALID, "out_dev overlaps packed_dev: the column is read while the result is written");
     if (table_dev && ranges_overlap(out_dev, out_bytes, table_dev, (table_rows * ct + 7) / 8))
         return fail(MI355_E_INVALID, "out_dev overlaps table_dev: the table is read while the result is written");
-    const uint64_t reach = lookup_reach(c, table_rows); // what a c-bit value can address of the table
+    const uint64_t reach = value_reach(c, table_rows); // what a c-bit value can address of the table
     LookupLaunch r{};
     r.k.packed = (const uint8_t *)packed_dev;
     r.k.n = n;
@@ -87,13 +79,8 @@ int mi355_lookup_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
     r.k.last_word = reach ? (uint32_t)((reach * ct - 1) >> 5) : 0u;
     r.k.miss = miss;
     r.k.nts = (uint32_t)one_pass_store_policy(out_bytes, ctx->scan_nt_stores);
-    r.stream = ctx->stream;
-    r.device = ctx->device;
-    r.num_cus = grid_cus(ctx);
-    r.max_blocks_per_cu = ctx->max_blocks_per_cu;
-    r.record = &ctx->last_launch;
-    ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache: the next eq / range scan is no repeat
-    ctx->llc_last_d = -1;
+    r.env = launch_env(ctx);
+    llc_forget(ctx);
     const hipError_t err = launch_by_width<1, 32>(ct, r, [](auto w, const LookupLaunch &q) { return launch_lookup<decltype(w)::value>(q); });
     if (err != hipSuccess) return fail(MI355_E_HIP, "lookup launch: %s", hipGetErrorString(err));
     return MI355_OK;

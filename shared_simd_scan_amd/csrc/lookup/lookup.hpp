@@ -57,7 +57,6 @@ struct LookupArgs {
     uint32_t nts;          // result stores: 0 plain, 1 non-temporal, 2 write-through (one uniform branch per tile)
 };
 
-constexpr uint32_t kLookupCuLds = 160 * 1024;
 constexpr int kLookupVpl = 32;                            // rows per lane and tile: the run-time-width decode's geometry
 constexpr int kLookupTileRows = 64 * kLookupVpl;          // 2048
 constexpr uint32_t kLookupLdsSlack = 64;                  // the dword behind the last lane's run, rounding to 16
@@ -67,17 +66,15 @@ constexpr uint32_t lookup_image(uint32_t c) { return (64u * kLookupVpl * c / 8 +
 // the waves' images of a block; + 16: the dword behind the last lane's run is read (and not used)
 constexpr uint32_t lookup_images_lds(uint32_t c) { return kWavesPerBlock * 2u * lookup_image(c) + 16u; }
 // MI355_LOOKUP_LDS_MAX_BYTES: what the widest images (c = 32) leave of a CU's LDS for the table and its `miss` entry
-constexpr uint32_t kLookupLdsMaxBytes = (kLookupCuLds - kWavesPerBlock * 2u * lookup_image(32) - kLookupLdsSlack) & ~15u;
+constexpr uint32_t kLookupLdsMaxBytes = (kCuLdsBytes - kWavesPerBlock * 2u * lookup_image(32) - kLookupLdsSlack) & ~15u;
 constexpr uint32_t lookup_entry_bytes(unsigned ct) { return ct <= 8 ? 1u : (ct <= 16 ? 2u : 4u); }
-// what a value of width c can reach of a table of table_rows rows
-constexpr uint64_t lookup_reach(unsigned c, uint64_t table_rows) { return (c < 32 && table_rows > (1ull << c)) ? (1ull << c) : table_rows; }
 constexpr bool lookup_in_lds(unsigned c, uint64_t table_rows, unsigned ct)
 {
-    return (lookup_reach(c, table_rows) + 1) * lookup_entry_bytes(ct) <= kLookupLdsMaxBytes;
+    return (value_reach(c, table_rows) + 1) * lookup_entry_bytes(ct) <= kLookupLdsMaxBytes;
 }
 // dynamic LDS of lookup_lds_kernel's table: reach + 1 entries, whole 16 bytes
 constexpr uint32_t lookup_table_lds(uint32_t reach, unsigned ct) { return ((reach + 1u) * lookup_entry_bytes(ct) + 15u) & ~15u; }
-static_assert(lookup_images_lds(32) + kLookupLdsMaxBytes <= kLookupCuLds, "LDS budget");
+static_assert(lookup_images_lds(32) + kLookupLdsMaxBytes <= kCuLdsBytes, "LDS budget");
 static_assert(kLookupLdsMaxBytes >= (4096u + 1u) * 4u, "a 12-bit key column's whole table fits at any output width");
 
 // ---- insert: value K of a lane's run of CT-bit results into its CT output dwords, the mirror of extract<C, K> ----

@@ -24,13 +24,13 @@ template <int C> constexpr size_t where_table_bytes(uint32_t P)
 {
     return ((size_t)((P + 7) / 8) * WhereLutGeom<C>::TABLE_BYTES + 15) / 16 * 16;
 }
-template <int C> constexpr bool where_tables_fit(uint32_t P) { return where_table_bytes<C>(P) + where_static_lds<C>() <= kCuLds; }
+template <int C> constexpr bool where_tables_fit(uint32_t P) { return where_table_bytes<C>(P) + where_static_lds<C>() <= kCuLdsBytes; }
 
 // blocks per CU of the table kernels: shared_lut_kernel's rule (lut_want_bpc), as far as the tables leave room
 template <int C> int where_lut_bpc(const WhereReq &r, bool linear, size_t lds_per_block)
 {
     const int want = lut_want_bpc(ScanGeom<C, kWhereVpl>::TILE_BYTES, linear, r.l.max_blocks_per_cu);
-    int fit = (int)(kCuLds / lds_per_block);
+    int fit = (int)(kCuLdsBytes / lds_per_block);
     if (fit < 1) fit = 1;
     return want < fit ? want : fit;
 }
@@ -77,7 +77,7 @@ template <int C> hipError_t launch_where(const WhereReq &r)
             // scans of more than 8 keys)
             const bool nt_stores = multi_pass_nt_stores((s.n / 8) * P, r.l.scan_nt_stores);
             const size_t dyn = where_table_bytes<C>(P);
-            const int max_dyn = (int)(kCuLds - where_static_lds<C>());
+            const int max_dyn = (int)(kCuLdsBytes - where_static_lds<C>());
             const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, dyn + where_static_lds<C>()), r.l.num_cus));
             if (linear)
                 launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, 1, true>>(r, grid, dyn, max_dyn);

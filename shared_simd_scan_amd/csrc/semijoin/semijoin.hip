@@ -1,6 +1,7 @@
 // semijoin.hip -- implementation of include/mi355_semijoin.h: argument checks, the choice between the two tiers and the launch
 // of semijoin_lds_kernel / semijoin_global_kernel (semijoin/semijoin.hpp) by width.  Its own translation unit: neither the other
-// entry points nor the width groups rebuild with it.
+// entry points nor the width groups rebuild with it.  The launch itself is launch_tier (launch_util.hpp) on a LaunchEnv (ctx.hpp),
+// shared with lookup/.
 #include "../ctx.hpp"
 
 #include "../../../include/mi355_semijoin.h"
@@ -22,17 +23,8 @@ struct SemiLaunch {
     unsigned c;
     bool in_lds;
     int store_policy; // one_pass_store_policy: 1 non-temporal, else write-through
-    hipStream_t stream;
-    int device, num_cus, max_blocks_per_cu;
-    std::string *record;
+    LaunchEnv env;
 };
-
-template <auto Kernel> void launch_tier(const SemiLaunch &r, uint64_t ntiles, size_t lds, size_t fixed_lds, int max_dyn)
-{
-    if (max_dyn > 0) allow_dynamic_lds<Kernel>(max_dyn, r.device);
-    const unsigned grid = grid_for(ntiles, cap_bpc(table_bpc<Kernel>(lds, fixed_lds, r.device), r.max_blocks_per_cu), r.num_cus);
-    MI355_LAUNCH(r.record, 0, Kernel, dim3(grid), dim3(kBlockThreads), lds, r.stream, r.k);
-}
 
 template <int C> hipError_t launch_semijoin(const SemiLaunch &r)
 {
@@ -42,11 +34,11 @@ template <int C> hipError_t launch_semijoin(const SemiLaunch &r)
     constexpr size_t fixed = semijoin_static_lds<C>() + 16u; // tiles, mask images, hits_finalize's flag
     if (r.in_lds) {
         const size_t lds = semijoin_dyn_lds(r.k.set_bytes);
-        const int max_dyn = (int)(kSemiCuLds - fixed);
-        nt ? launch_tier<semijoin_lds_kernel<C, 18>>(r, ntiles, lds, fixed, max_dyn) : launch_tier<semijoin_lds_kernel<C, 34>>(r, ntiles, lds, fixed, max_dyn);
+        const int max_dyn = (int)(kCuLdsBytes - fixed);
+        nt ? launch_tier<semijoin_lds_kernel<C, 18>>(r.env, r.k, ntiles, lds, fixed, max_dyn) : launch_tier<semijoin_lds_kernel<C, 34>>(r.env, r.k, ntiles, lds, fixed, max_dyn);
     } else {
         if constexpr (C >= kSemiGlobalMinBits)
-            nt ? launch_tier<semijoin_global_kernel<C, 18>>(r, ntiles, 0, fixed, 0) : launch_tier<semijoin_global_kernel<C, 34>>(r, ntiles, 0, fixed, 0);
+            nt ? launch_tier<semijoin_global_kernel<C, 18>>(r.env, r.k, ntiles, 0, fixed, 0) : launch_tier<semijoin_global_kernel<C, 34>>(r.env, r.k, ntiles, 0, fixed, 0);
         else
             return hipErrorInvalidValue; // semijoin_in_lds() is true below kSemiGlobalMinBits
     }
@@ -80,7 +72,7 @@ int mi355_semijoin_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsig
         return MI355_OK;
     }
     MI355_CHECK(check_dev(packed_dev, 16, "packed_dev"));
-    const uint64_t reach = semijoin_reach(c, set_bits); // what a c-bit value can address of the set
+    const uint64_t reach = value_reach(c, set_bits); // what a c-bit value can address of the set
     SemiLaunch r{};
     r.k.s.packed = (const uint8_t *)packed_dev;
     r.k.s.n = n;
@@ -97,13 +89,8 @@ int mi355_semijoin_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsig
     r.c = c;
     r.in_lds = semijoin_in_lds(c, set_bits);
     r.store_policy = one_pass_store_policy(n / 8, ctx->scan_nt_stores);
-    r.stream = ctx->stream;
-    r.device = ctx->device;
-    r.num_cus = grid_cus(ctx);
-    r.max_blocks_per_cu = ctx->max_blocks_per_cu;
-    r.record = &ctx->last_launch;
-    ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache: the next eq / range scan is no repeat
-    ctx->llc_last_d = -1;
+    r.env = launch_env(ctx);
+    llc_forget(ctx);
     const hipError_t err = launch_by_width<1, 32>(c, r, [](auto w, const SemiLaunch &q) { return launch_semijoin<decltype(w)::value>(q); });
     if (err != hipSuccess) return fail(MI355_E_HIP, "semijoin launch: %s", hipGetErrorString(err));
     return MI355_OK;

@@ -50,7 +50,6 @@ struct SemiArgs {
     uint32_t last_keep;  // mask of the valid bits of byte set_bytes - 1 (0xff: all eight)
 };
 
-constexpr uint32_t kSemiCuLds = 160 * 1024;
 constexpr uint32_t kSemiMaskLds = 1024; // a tile's AND-mask bytes per wave: one LDS-DMA instruction
 constexpr uint32_t kSemiLdsSlack = 64;  // hits_finalize's flag, the image's zero byte, rounding to 16
 constexpr int kSemiGlobalMinBits = 20;  // the global tier exists from this width on (2^19 < the LDS ceiling)
@@ -64,17 +63,15 @@ template <int C> constexpr uint32_t semijoin_static_lds()
 constexpr uint64_t semijoin_lds_max_bits()
 {
     constexpr uint32_t widest = semijoin_static_lds<32>() > semijoin_static_lds<16>() ? semijoin_static_lds<32>() : semijoin_static_lds<16>();
-    return 8ull * ((kSemiCuLds - widest - kSemiLdsSlack) & ~15u);
+    return 8ull * ((kCuLdsBytes - widest - kSemiLdsSlack) & ~15u);
 }
 static_assert(semijoin_lds_max_bits() >= (1ull << 19), "the LDS tier serves at least what histogram keeps next to its tiles");
 static_assert(semijoin_lds_max_bits() < (1ull << kSemiGlobalMinBits), "widths below kSemiGlobalMinBits never reach the global tier");
-// what a value of width c can reach of a set of set_bits bits
-constexpr uint64_t semijoin_reach(unsigned c, uint64_t set_bits) { return (c < 32 && set_bits > (1ull << c)) ? (1ull << c) : set_bits; }
-constexpr bool semijoin_in_lds(unsigned c, uint64_t set_bits) { return semijoin_reach(c, set_bits) <= semijoin_lds_max_bits(); }
+constexpr bool semijoin_in_lds(unsigned c, uint64_t set_bits) { return value_reach(c, set_bits) <= semijoin_lds_max_bits(); }
 // dynamic LDS of semijoin_lds_kernel for a set of set_bytes bytes: the image, its zero byte, whole 16 bytes
 constexpr uint32_t semijoin_dyn_lds(uint32_t set_bytes) { return (set_bytes + 1u + 15u) & ~15u; }
-static_assert(semijoin_static_lds<32>() + 16u + semijoin_dyn_lds((uint32_t)(semijoin_lds_max_bits() / 8)) <= kSemiCuLds, "LDS budget");
-static_assert(semijoin_static_lds<16>() + 16u + semijoin_dyn_lds((uint32_t)(semijoin_lds_max_bits() / 8)) <= kSemiCuLds, "LDS budget");
+static_assert(semijoin_static_lds<32>() + 16u + semijoin_dyn_lds((uint32_t)(semijoin_lds_max_bits() / 8)) <= kCuLdsBytes, "LDS budget");
+static_assert(semijoin_static_lds<16>() + 16u + semijoin_dyn_lds((uint32_t)(semijoin_lds_max_bits() / 8)) <= kCuLdsBytes, "LDS budget");
 
 // [from, to) of the set -> LDS with 4-byte loads, then single bytes; `from` is a multiple of 4
 __device__ __forceinline__ void semijoin_copy_narrow(const uint8_t *set, uint8_t *image, uint32_t from, uint32_t to)

@@ -42,7 +42,6 @@ inline SharedPlan make_plan(SharedForm form, int want_bpc, int vpl = 64) { retur
 
 // ---- LDS budgets ---------------------------------------------------------------------------------------------------------
 
-constexpr size_t kCuLds = 160 * 1024;
 constexpr int kSharedVpl = scan_vpl(0, kModeShared); // 64 values per lane and tile, but for the pair and the one-pass LUT kernels
 
 // static LDS of the multi-pass LUT kernel: four tiles, the per-block hit counters, ticket word and slack
@@ -52,16 +51,16 @@ template <int C, int VPL> constexpr size_t lut_static_lds()
     return 4 * ScanGeom<C, VPL>::LDS_BYTES + kMaxKeys * 4 + 512 + (C <= 12 ? (size_t)(4u << C) : 16);
 }
 // what the kernels with tables in dynamic LDS may be given
-template <int C> constexpr int shared_max_dyn_lds() { return (int)(kCuLds - lut_static_lds<C, kSharedVpl>()); }
+template <int C> constexpr int shared_max_dyn_lds() { return (int)(kCuLdsBytes - lut_static_lds<C, kSharedVpl>()); }
 
 // one dword-entry table per 32 keys (WideLutGeom) / one byte-entry table per 8 keys (LutGeom<C, true>), in dynamic LDS
 template <int C, bool BIG = false> constexpr size_t wide_table_bytes(uint32_t P) { return (size_t)((P + 31) / 32) * WideLutGeom<C, BIG>::TABLE_BYTES; }
 template <int C> constexpr size_t lut8_table_bytes(uint32_t P) { return ((size_t)((P + 7) / 8) * LutGeom<C, true>::TABLE_BYTES + 15) / 16 * 16; }
 
 // the 32-keys-per-lookup kernels need ceil(P/32) tables next to the static part in the CU's 160 KiB of LDS
-template <int C, int VPL> constexpr bool lut_fits(uint32_t P) { return wide_table_bytes<C>(P) + lut_static_lds<C, VPL>() <= kCuLds; }
+template <int C, int VPL> constexpr bool lut_fits(uint32_t P) { return wide_table_bytes<C>(P) + lut_static_lds<C, VPL>() <= kCuLdsBytes; }
 // ... and the byte-entry multi-pass kernel ceil(P/8) tables
-template <int C, int VPL> constexpr bool lut8_fits(uint32_t P) { return lut8_table_bytes<C>(P) + lut_static_lds<C, VPL>() <= kCuLds; }
+template <int C, int VPL> constexpr bool lut8_fits(uint32_t P) { return lut8_table_bytes<C>(P) + lut_static_lds<C, VPL>() <= kCuLdsBytes; }
 
 // shared_linear3_kernel: four tiles and the 33 KiB row stage next to the tables
 template <int C> constexpr size_t linear3_fixed_lds() { return 4 * ScanGeom<C, 64>::LDS_BYTES + 33 * 1024; }
@@ -152,11 +151,11 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
     // 4.33, P = 24 / 31 equal), a long second round (its 32-byte pieces complete the first round's half-written lines a
     // whole round later: P = 48 3.01 against 3.41, P = 64 2.29 against 3.94), and widths whose tiles leave room for one
     // block per CU only (c = 25, P = 32: 2.95 against 4.40).
-    if (linear && P >= 32 && P <= 40 && !(flags & kSwNoLinear3) && 2 * (wide_table_bytes<C>(P) + linear3_fixed_lds<C>()) <= kCuLds) {
+    if (linear && P >= 32 && P <= 40 && !(flags & kSwNoLinear3) && 2 * (wide_table_bytes<C>(P) + linear3_fixed_lds<C>()) <= kCuLdsBytes) {
         bool big = false;
-        if constexpr (kBigWidth) big = !(flags & kSwByteDigits) && 2 * (wide_table_bytes<C, true>(P) + linear3_fixed_lds<C>()) <= kCuLds;
+        if constexpr (kBigWidth) big = !(flags & kSwByteDigits) && 2 * (wide_table_bytes<C, true>(P) + linear3_fixed_lds<C>()) <= kCuLdsBytes;
         const size_t dyn3 = big ? wide_table_bytes<C, true>(P) : wide_table_bytes<C>(P);
-        const int fit = (int)(kCuLds / (dyn3 + linear3_fixed_lds<C>()));
+        const int fit = (int)(kCuLdsBytes / (dyn3 + linear3_fixed_lds<C>()));
         return make_plan(kFormLinear3, cap_bpc(fit > 2 ? 2 : (fit < 1 ? 1 : fit), max_bpc)).lds(dyn3).counters(hits ? (P <= 32 ? 1 : 2) : 0, big);
     }
 
@@ -171,7 +170,7 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
     // c = 9, P = 300: 3.6 / 4.1 against 2.2 / 2.3).
     const bool lin_pays = C <= 10 || (C <= 16 ? P <= 320 : P <= (hits ? 320u : 160u)) || (flags & kSwLinearAnyWidth); // (always, A/B)
     const bool lin_rows = linear && lut_fits<C, VPL>(P) && !(flags & kSwPerGroupKernels) && lin_pays &&
-                          (2 * (wide_table_bytes<C>(P) + lut_static_lds<C, VPL>()) <= kCuLds || (hits && WideLutGeom<C>::SINGLE));
+                          (2 * (wide_table_bytes<C>(P) + lut_static_lds<C, VPL>()) <= kCuLdsBytes || (hits && WideLutGeom<C>::SINGLE));
 
     // ---- 4. linear rows of fewer than ~200 keys without hit counts, where the row-per-lane kernels do not run: byte-entry
     // tables, 16 output bytes per round (measured, tools/sweep_p.py, 2.5e8 x 9 bit: P = 16 / 32 / 64 / 128 0.21 / 0.43 / 0.72 /
@@ -237,7 +236,7 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
         const bool hist_counts = C <= 12 && P >= 64;
         const int rc = (hits && !(flags & kSwCountsByReduction)) ? (P <= 32 ? 1 : ((P <= 64 && !hist_counts) ? 2 : 0)) : 0;
         bool big = false;
-        if constexpr (kBigWidth) big = !(flags & kSwByteDigits) && 2 * (wide_table_bytes<C, true>(P) + lut_static_lds<C, VPL>()) <= kCuLds;
+        if constexpr (kBigWidth) big = !(flags & kSwByteDigits) && 2 * (wide_table_bytes<C, true>(P) + lut_static_lds<C, VPL>()) <= kCuLdsBytes;
         const size_t bdyn = big ? wide_table_bytes<C, true>(P) : dyn;
         // a 32-value word at a time (shared_wide3_kernel: half the registers, several waves per SIMD -- what the digit-table
         // widths need, and 0-20 % ahead at c <= 10 too: 2.5e8 x 9 bit, P = 9 / 24 / 63, TB/s with / without hit counts:
@@ -245,7 +244,7 @@ template <int C> SharedPlan plan_shared(const LaunchReq &r)
         // without hit counts, or up to 64 keys (kSwWide2: shared_wide2_kernel, A/B)
         if ((!hits || rc != 0) && !(flags & kSwWide2)) {
             const int waves = (rc == 0 || C <= 10) ? 3 : 2; // the kernel's launch bound
-            const int fit = (int)(kCuLds / (bdyn + 4 * ScanGeom<C, 64>::LDS_BYTES + 256));
+            const int fit = (int)(kCuLdsBytes / (bdyn + 4 * ScanGeom<C, 64>::LDS_BYTES + 256));
             return make_plan(kFormWide3, cap_bpc(fit > waves ? waves : (fit < 1 ? 1 : fit), max_bpc)).lds(bdyn).counters(rc, big).stores(store);
         }
         // (register counters in shared_wide2_kernel only at the single-table widths: the digit-table widths that come here

@@ -142,7 +142,7 @@ template <int C> void launch_shared(const LaunchReq &r, const SharedPlan &p)
         break;
     case kFormLinear3:
         with_rc_big<2, kBigWidth>(p.rc, p.big, [&](auto rc, auto big) {
-            launch_planned<shared_linear3_kernel<C, 2, rc.value, big.value>>(r, p, p.want_bpc, (int)(kCuLds - linear3_fixed_lds<C>()));
+            launch_planned<shared_linear3_kernel<C, 2, rc.value, big.value>>(r, p, p.want_bpc, (int)(kCuLdsBytes - linear3_fixed_lds<C>()));
         });
         break;
     case kFormLutMulti: launch_planned<shared_lut_kernel<C, 2, VPL, 1, true>>(r, p, p.want_bpc, max_dyn); break;

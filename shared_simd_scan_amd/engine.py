@@ -116,26 +116,32 @@ def shared_where_kernel(c: int, P: int, layout: str = "per_predicate", with_hits
     return s.decode()
 
 
+def _table_kernel(query, count: int, what: tuple) -> str:
+    """the kernel family by the size of a device-resident set or table: `count` outside 0..2^32 (ctypes would wrap it) or an
+    answer of NULL (a width the library does not have) -> ValueError(what)"""
+    if not 0 <= int(count) <= 1 << 32:
+        raise ValueError(what)
+    s = query()
+    if s is None:
+        raise ValueError(what)
+    return s.decode()
+
+
 def semi_join_kernel(c: int, set_bits: int) -> str:
     """kernel family ScanEngine.semi_join launches for a set of set_bits bits at width c (mi355_semijoin_kernel; arithmetic
     only, needs no device): 'semijoin_lds_kernel' | 'semijoin_global_kernel'"""
-    if not 0 <= int(set_bits) <= 1 << 32:
-        raise ValueError((c, set_bits))
-    s = lib().mi355_semijoin_kernel(c, int(set_bits))
-    if s is None:
-        raise ValueError((c, set_bits))
-    return s.decode()
+    return _table_kernel(lambda: lib().mi355_semijoin_kernel(c, int(set_bits)), set_bits, (c, set_bits))
 
 
 def lookup_kernel(c: int, table_rows: int, ct: int) -> str:
     """kernel family ScanEngine.lookup launches for a column of width c and a table of table_rows values of width ct
     (mi355_lookup_kernel; arithmetic only, needs no device): 'lookup_lds_kernel' | 'lookup_global_kernel'"""
-    if not 0 <= int(table_rows) <= 1 << 32:
-        raise ValueError((c, table_rows, ct))
-    s = lib().mi355_lookup_kernel(c, int(table_rows), ct)
-    if s is None:
-        raise ValueError((c, table_rows, ct))
-    return s.decode()
+    return _table_kernel(lambda: lib().mi355_lookup_kernel(c, int(table_rows), ct), table_rows, (c, table_rows, ct))
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """an optional tensor as a pointer argument: None travels as NULL"""
+    return t.data_ptr() if t is not None else None
 
 
 class PackedColumn:
@@ -248,13 +254,21 @@ class ScanEngine:
     def alloc_bitmap(self, n: int) -> torch.Tensor:
         return self._empty((n + 7) // 8)
 
+    def _outputs(self, n: int, bitmap, hits, count_only: bool = False):
+        """the scans' output defaults -> (bitmap, hits): a bitmap of n rows unless one is given (none at all with count_only),
+        one int64 hit count unless one is given"""
+        if count_only:
+            bitmap = None
+        elif bitmap is None:
+            bitmap = self.alloc_bitmap(n)
+        if hits is None:
+            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        return bitmap, hits
+
     def scan(self, key: int, col: PackedColumn, bitmap: Optional[torch.Tensor] = None,
              hits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """value == key -> (bitmap uint8[ceil(n/8)], hits int64[1]); asynchronous on the stream."""
-        if bitmap is None:
-            bitmap = self.alloc_bitmap(col.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col.n, bitmap, hits)
         check(lib().mi355_scan_eq_dev(self._ctx, col.data.data_ptr(), col.n, col.c, key32(key, col.c), bitmap.data_ptr(),
                                       hits.data_ptr()))
         return bitmap, hits
@@ -262,10 +276,7 @@ class ScanEngine:
     def scan_range(self, lo: int, hi: int, col: PackedColumn, bitmap: Optional[torch.Tensor] = None,
                    hits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """lo <= value <= hi (src/simd_scan.hpp:76-84); any ints, compared exactly."""
-        if bitmap is None:
-            bitmap = self.alloc_bitmap(col.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col.n, bitmap, hits)
         lo, hi = range_bounds(lo, hi) or (1, 0)  # lo > hi: the C side stores the empty result
         check(lib().mi355_scan_range_dev(self._ctx, col.data.data_ptr(), col.n, col.c, lo, hi, bitmap.data_ptr(),
                                          hits.data_ptr()))
@@ -278,13 +289,9 @@ class ScanEngine:
     def scan_where(self, op: str, a: int, col: PackedColumn, b: int = 0, and_mask: Optional[torch.Tensor] = None,
                    bitmap: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):
         """bitmap[i] = (value_i OP a [, b]) [& and_mask[i]]; op in == != < <= > >= between not_between."""
-        if bitmap is None:
-            bitmap = self.alloc_bitmap(col.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col.n, bitmap, hits)
         check(lib().mi355_scan_where_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
-                                         and_mask.data_ptr() if and_mask is not None else None, bitmap.data_ptr(),
-                                         hits.data_ptr()))
+                                         _ptr(and_mask), bitmap.data_ptr(), hits.data_ptr()))
         return bitmap, hits
 
     def scan_combine(self, op: str, a: int, col: PackedColumn, b: int = 0, mask: Optional[torch.Tensor] = None,
@@ -292,14 +299,10 @@ class ScanEngine:
                      count_only: bool = False):
         """scan_where with the earlier bitmap combined by AND / OR / XOR / ANDNOT (mask & ~p) inside the scan;
         count_only=True stores no bitmap at all (returns (None, hits))."""
-        if bitmap is None and not count_only:
-            bitmap = self.alloc_bitmap(col.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col.n, bitmap, hits, count_only)
         check(lib().mi355_scan_combine_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
-                                           self._BOP[mask_op], mask.data_ptr() if mask is not None else None,
-                                           None if count_only else bitmap.data_ptr(), hits.data_ptr()))
-        return (None if count_only else bitmap), hits
+                                           self._BOP[mask_op], _ptr(mask), _ptr(bitmap), hits.data_ptr()))
+        return bitmap, hits
 
     def scan2(self, col1: PackedColumn, op1: str, a1: int, col2: PackedColumn, op2: str, a2: int, b1: int = 0, b2: int = 0,
               combine: str = "and", bitmap: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None,
@@ -307,14 +310,11 @@ class ScanEngine:
         """predicates over two columns of the same row count, combined (and / or / xor / andnot = p1 & ~p2) in one call;
         same-width columns run as a single launch"""
         assert col1.n == col2.n
-        if bitmap is None and not count_only:
-            bitmap = self.alloc_bitmap(col1.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col1.n, bitmap, hits, count_only)
         check(lib().mi355_scan2_dev(self._ctx, col1.data.data_ptr(), col1.c, self._CMP[op1], clamp_const(a1), clamp_const(b1),
                                     col2.data.data_ptr(), col2.c, self._CMP[op2], clamp_const(a2), clamp_const(b2), col1.n, self._BOP[combine],
-                                    None if count_only else bitmap.data_ptr(), hits.data_ptr()))
-        return (None if count_only else bitmap), hits
+                                    _ptr(bitmap), hits.data_ptr()))
+        return bitmap, hits
 
     def scan_columns(self, col1: PackedColumn, op: str, col2: PackedColumn, a: int = 0, b: int = 0, mask: Optional[torch.Tensor] = None,
                      mask_op: str = "and", bitmap: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None,
@@ -323,14 +323,10 @@ class ScanEngine:
         col1 >= col2 + 30 is (">=", a=30), |col1 - col2| <= 3 is ("between", a=-3, b=3).  Any width pair, one launch; mask,
         mask_op, bitmap, hits and count_only as in scan_combine."""
         assert col1.n == col2.n
-        if bitmap is None and not count_only:
-            bitmap = self.alloc_bitmap(col1.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col1.n, bitmap, hits, count_only)
         check(lib().mi355_scan_columns_dev(self._ctx, col1.data.data_ptr(), col1.c, col2.data.data_ptr(), col2.c, col1.n, self._CMP[op],
-                                           clamp_diff(a), clamp_diff(b), self._BOP[mask_op], mask.data_ptr() if mask is not None else None,
-                                           None if count_only else bitmap.data_ptr(), hits.data_ptr()))
-        return (None if count_only else bitmap), hits
+                                           clamp_diff(a), clamp_diff(b), self._BOP[mask_op], _ptr(mask), _ptr(bitmap), hits.data_ptr()))
+        return bitmap, hits
 
     def scan_select(self, op: str, a: int, col: PackedColumn, capacity: int, b: int = 0, mask: Optional[torch.Tensor] = None,
                     mask_op: str = "and", first_row: int = 0):
@@ -339,7 +335,7 @@ class ScanEngine:
         rowids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self._dev)
         count = torch.empty(1, dtype=torch.int64, device=self._dev)
         check(lib().mi355_scan_select_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
-                                          self._BOP[mask_op], mask.data_ptr() if mask is not None else None, first_row,
+                                          self._BOP[mask_op], _ptr(mask), first_row,
                                           rowids.data_ptr(), capacity, count.data_ptr()))
         return rowids, count
 
@@ -349,13 +345,9 @@ class ScanEngine:
         """bitmap[i] = value_i in keys (NOT IN with negate=True) [& and_mask[i]].  Every P is uploaded per call; never
         capturable into a graph (refused while the stream is capturing)."""
         k = keys32(keys, col.c)
-        if bitmap is None:
-            bitmap = self.alloc_bitmap(col.n)
-        if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+        bitmap, hits = self._outputs(col.n, bitmap, hits)
         check(lib().mi355_scan_in_dev(self._ctx, col.data.data_ptr(), col.n, col.c, k.ctypes.data, int(k.shape[0]),
-                                      1 if negate else 0, and_mask.data_ptr() if and_mask is not None else None,
-                                      bitmap.data_ptr(), hits.data_ptr()))
+                                      1 if negate else 0, _ptr(and_mask), bitmap.data_ptr(), hits.data_ptr()))
         return bitmap, hits
 
     def semi_join(self, col: PackedColumn, set_bitmap: Optional[torch.Tensor], set_bits: int, negate: bool = False,
@@ -377,9 +369,9 @@ class ScanEngine:
         if bitmap is None:
             bitmap = self.alloc_bitmap(col.n)
         hits = torch.empty(1, dtype=torch.int64, device=self._dev) if want_hits else None
-        check(lib().mi355_semijoin_dev(self._ctx, col.data.data_ptr(), col.n, col.c, set_bitmap.data_ptr() if set_bitmap is not None else None,
-                                       set_bits, 1 if negate else 0, and_mask.data_ptr() if and_mask is not None else None,
-                                       None if count_only else bitmap.data_ptr(), hits.data_ptr() if want_hits else None))
+        check(lib().mi355_semijoin_dev(self._ctx, col.data.data_ptr(), col.n, col.c, _ptr(set_bitmap),
+                                       set_bits, 1 if negate else 0, _ptr(and_mask),
+                                       None if count_only else bitmap.data_ptr(), _ptr(hits)))
         return (None if count_only else bitmap), hits
 
     def lookup(self, col: PackedColumn, table: PackedColumn, miss: int = 0, out: Optional[torch.Tensor] = None) -> PackedColumn:
@@ -438,8 +430,7 @@ class ScanEngine:
         None = every row): one pass over the column, nothing decoded to memory.  count = 0: min is -1 (UINT64_MAX)."""
         if out is None:
             out = torch.empty(4, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_aggregate_dev(self._ctx, col.data.data_ptr(), col.n, col.c, mask.data_ptr() if mask is not None else None,
-                                        out.data_ptr()))
+        check(lib().mi355_aggregate_dev(self._ctx, col.data.data_ptr(), col.n, col.c, _ptr(mask), out.data_ptr()))
         return out
 
     def histogram(self, col: PackedColumn, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -447,8 +438,7 @@ class ScanEngine:
         if out is None:
             out = torch.empty(1 << col.c, dtype=torch.int64, device=self._dev)
         assert out.numel() >= (1 << col.c) and out.dtype == torch.int64
-        check(lib().mi355_histogram_dev(self._ctx, col.data.data_ptr(), col.n, col.c, mask.data_ptr() if mask is not None else None,
-                                        out.data_ptr()))
+        check(lib().mi355_histogram_dev(self._ctx, col.data.data_ptr(), col.n, col.c, _ptr(mask), out.data_ptr()))
         return out
 
     def group_aggregate(self, keys: PackedColumn, values: PackedColumn, mask: Optional[torch.Tensor] = None,
@@ -461,11 +451,26 @@ class ScanEngine:
         if out is None:
             out = torch.empty((groups, 4), dtype=torch.int64, device=self._dev)
         assert tuple(out.shape) == (groups, 4) and out.dtype == torch.int64 and out.is_contiguous()
-        check(lib().mi355_group_aggregate_dev(self._ctx, keys.data.data_ptr(), keys.c, values.data.data_ptr(), values.c, keys.n,
-                                              mask.data_ptr() if mask is not None else None, out.data_ptr()))
+        check(lib().mi355_group_aggregate_dev(self._ctx, keys.data.data_ptr(), keys.c, values.data.data_ptr(), values.c, keys.n, _ptr(mask), out.data_ptr()))
         return out
 
     # ---- shared scans (src/simd_scan_shared.cpp, src/simd_scan_shared_linear.cpp) -----------------
+    def _shared_outputs(self, n: int, P: int, layout: str, out, hits):
+        """the outputs of a shared scan of P keys / predicates by layout -> (out, hits, hits pointer, layout code, stride)"""
+        if hits is None:
+            hits = torch.empty(P, dtype=torch.int64, device=self._dev)
+        hits_ptr = 0 if hits is False else hits.data_ptr()  # hits=False: bitmaps only, no counting
+        if layout == "per_predicate":
+            stride = int(lib().mi355_bitmap_stride(n))  # whole 128-byte lines per bitmap: up to 2x faster than a 16-byte-multiple stride
+            if out is None:
+                out = torch.empty((P, stride), dtype=torch.uint8, device=self._dev)
+            return out, hits, hits_ptr, _capi.LAYOUT_PER_PREDICATE, stride
+        if layout == "linear":
+            if out is None:
+                out = self._empty((n + 7) // 8 * P)
+            return out, hits, hits_ptr, _capi.LAYOUT_LINEAR, 0
+        raise ValueError(layout)
+
     def shared_scan(self, keys: Sequence[int], col: PackedColumn, layout: str = "per_predicate",
                     out: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):
         """per_predicate -> uint8[P, stride] (row k = bitmap of keys[k], stride = mi355_bitmap_stride(n): ceil(n/8) rounded up to 256);
@@ -473,22 +478,7 @@ class ScanEngine:
         hits: int64[P] device tensor to fill (allocated when None); False skips the hit counts."""
         k = keys32(keys, col.c)
         P = int(k.shape[0])
-        nb = (col.n + 7) // 8
-        if hits is None:
-            hits = torch.empty(P, dtype=torch.int64, device=self._dev)
-        hits_ptr = 0 if hits is False else hits.data_ptr()  # hits=False: bitmaps only, no counting
-        if layout == "per_predicate":
-            stride = int(lib().mi355_bitmap_stride(col.n))  # whole 128-byte lines per bitmap: up to 2x faster than a 16-byte-multiple stride
-            if out is None:
-                out = torch.empty((P, stride), dtype=torch.uint8, device=self._dev)
-            code = _capi.LAYOUT_PER_PREDICATE
-        elif layout == "linear":
-            stride = 0
-            if out is None:
-                out = self._empty(nb * P)
-            code = _capi.LAYOUT_LINEAR
-        else:
-            raise ValueError(layout)
+        out, hits, hits_ptr, code, stride = self._shared_outputs(col.n, P, layout, out, hits)
         check(lib().mi355_shared_scan_eq_dev(self._ctx, col.data.data_ptr(), col.n, col.c, k.ctypes.data, P, code,
                                              out.data_ptr(), stride, hits_ptr))
         return out, (None if hits is False else hits)
@@ -500,22 +490,7 @@ class ScanEngine:
         value as shared_scan."""
         arr = predicates(preds)
         P = len(preds)
-        nb = (col.n + 7) // 8
-        if hits is None:
-            hits = torch.empty(P, dtype=torch.int64, device=self._dev)
-        hits_ptr = 0 if hits is False else hits.data_ptr()
-        if layout == "per_predicate":
-            stride = int(lib().mi355_bitmap_stride(col.n))
-            if out is None:
-                out = torch.empty((P, stride), dtype=torch.uint8, device=self._dev)
-            code = _capi.LAYOUT_PER_PREDICATE
-        elif layout == "linear":
-            stride = 0
-            if out is None:
-                out = self._empty(nb * P)
-            code = _capi.LAYOUT_LINEAR
-        else:
-            raise ValueError(layout)
+        out, hits, hits_ptr, code, stride = self._shared_outputs(col.n, P, layout, out, hits)
         check(lib().mi355_shared_scan_where_dev(self._ctx, col.data.data_ptr(), col.n, col.c, C.cast(arr, C.c_void_p), P, code,
                                                 out.data_ptr(), stride, hits_ptr))
         return out, (None if hits is False else hits)

@@ -1,25 +1,14 @@
 """CPU: the C-ABI library loads and exports every symbol include/mi355_scan.h declares (no compute)."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def L():
-    from shared_simd_scan_amd import build, lib
-
-    if not os.path.exists(build.LIB_PATH):
-        build.build()
-    return lib()
+from support import ROOT, L, declared  # noqa: F401  (L: a fixture)
 
 
 def header_symbols():
-    text = open(os.path.join(ROOT, "include", "mi355_scan.h")).read()
-    return sorted(set(re.findall(r"^MI355_API [^;(]*?\b(mi355_\w+)\(", text, flags=re.M)))
+    return declared("mi355_scan.h")
 
 
 def test_header_declares_what_python_binds():

@@ -22,6 +22,7 @@ def vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# differs from support.L: a missing library is an error here, it is not built
 @pytest.fixture(scope="module")
 def L():
     from shared_simd_scan_amd import lib
@@ -29,6 +30,7 @@ def L():
     return lib()
 
 
+# differs from support.eng: says why when there is no GPU, takes the current device, is never closed
 @pytest.fixture(scope="module")
 def eng():
     import torch

@@ -677,6 +677,7 @@ _case("dev_memset", case_dev_memset)
 _case("n0_forms", case_n0_forms)
 
 
+# differs from support.L: says why when there is no GPU, and a missing library is an error
 @pytest.fixture(scope="module")
 def L():
     import torch

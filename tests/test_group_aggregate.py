@@ -14,20 +14,14 @@ one tile per wave of a block, and many tiles with a ragged tail.
 """
 import ctypes as C
 import functools
-import glob
-import os
-import re
-import subprocess
-import types
 
 import numpy as np
 import pytest
 
-from test_kernel_paths import SENTINEL, Guarded, packbits, parse_record
+import support
+from support import L, eng, fake, record, upload  # noqa: F401  (L, eng, fake: fixtures)
+from test_kernel_paths import SENTINEL, Guarded, packbits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-GROUPBY_DIR = os.path.join(ROOT, "shared_simd_scan_amd", "csrc", "groupby")
 HEADER = "mi355_groupby.h"
 E_INVALID = -1
 U64_MAX = (1 << 64) - 1
@@ -106,87 +100,21 @@ def expect(keys, vals, ck, mask_bits=None):
 # CPU
 # ---------------------------------------------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def L():
-    from shared_simd_scan_amd import build, lib
-
-    if not os.path.exists(build.LIB_PATH):
-        build.build()
-    return lib()
-
-
-def declared(header):
-    text = open(os.path.join(INCLUDE, header)).read()
-    return sorted(set(re.findall(r"^MI355_API [^;(]*?\b(mi355_\w+)\(", text, flags=re.M)))
-
-
 def test_groupby_header_is_plain_c99():
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c", os.path.join(INCLUDE, HEADER)],
-                   check=True)
+    support.check_header_is_plain_c99(HEADER)
 
 
 def test_groupby_header_declares_what_python_binds(L):
     from shared_simd_scan_amd import _capi
 
-    names = declared(HEADER)
-    assert names == sorted(s[0] for s in _capi.GROUP_SYMBOLS) and names == ["mi355_group_aggregate_dev"]
-    for name in names:
-        assert hasattr(L, name), name
-        assert getattr(L, name).argtypes == dict((s[0], s[2]) for s in _capi.GROUP_SYMBOLS)[name]  # lib() applied the list
-    for other in ("mi355_scan.h", "mi355_columns.h"):
-        assert not set(names) & set(declared(other)), other
-        assert HEADER not in open(os.path.join(INCLUDE, other)).read(), f"{other} includes {HEADER}"
-    assert not set(names) & {s[0] for s in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS}
-    sig = dict((s[0], s[2]) for s in _capi.GROUP_SYMBOLS)["mi355_group_aggregate_dev"]
+    names, sigs = support.check_header_binds(L, HEADER, _capi.GROUP_SYMBOLS, ("mi355_scan.h", "mi355_columns.h"), _capi.SYMBOLS + _capi.COLUMN_SYMBOLS)
+    assert names == ["mi355_group_aggregate_dev"]
+    sig = sigs["mi355_group_aggregate_dev"]
     assert sig[2] is C.c_uint and sig[4] is C.c_uint and sig[5] is C.c_uint64 and len(sig) == 8
 
 
 def test_groupby_header_carries_its_capture_verdict():
-    text = open(os.path.join(INCLUDE, HEADER)).read()
-    assert re.search(r"graph capture: capturable\b", text)
-
-
-class _RecordingLib:
-    """stand-in for libmi355scan.so: converts the arguments through the real argtypes (as ctypes would) and records them"""
-
-    def __init__(self):
-        from shared_simd_scan_amd import _capi
-
-        self.calls = []
-        self._sig = {name: args for name, _, args in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS}
-
-    def __getattr__(self, name):
-        argtypes = self._sig[name]
-
-        def call(*args):
-            assert len(args) == len(argtypes), name
-            conv = []
-            for t, a in zip(argtypes, args):
-                if t in (C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_int, C.c_uint) and isinstance(a, int):
-                    a = t(a).value
-                conv.append(a)
-            self.calls.append((name, conv))
-            return 0
-
-        return call
-
-
-@pytest.fixture
-def fake(monkeypatch):
-    import torch
-
-    from shared_simd_scan_amd import engine
-
-    rec = _RecordingLib()
-    monkeypatch.setattr(engine, "lib", lambda: rec)
-    monkeypatch.setattr(engine, "check", lambda rc: None)
-    eng = object.__new__(engine.ScanEngine)
-    eng._ctx, eng._dev = None, torch.device("cpu")
-
-    def col(c, n=1000):
-        return types.SimpleNamespace(data=torch.zeros(64, dtype=torch.uint8), n=n, c=c)
-
-    return eng, rec, col
+    support.check_capture_verdict(HEADER)
 
 
 def test_group_aggregate_wrapper_passes_what_the_abi_takes(fake):
@@ -231,29 +159,17 @@ def test_group_entry_point_fails_loudly_without_a_gpu(L):
     assert rc != 0 and L.mi355_last_error()
 
 
-def groupby_sources():
-    return sorted(glob.glob(os.path.join(GROUPBY_DIR, "*.hpp")) + glob.glob(os.path.join(GROUPBY_DIR, "*.hip")))
-
-
 def test_every_groupby_kernel_has_a_case():
     """the rule test_shared_where_cpu.py applies to csrc/predicates/: every __global__ under csrc/groupby/ is asserted from the
     launch record by a GPU case of this file (INIT_KERNEL: test_errors_launch_nothing, AGG_KERNEL: test_sizes_and_tails and
     others), and the file names no kernel that does not exist"""
-    kernels = set()
-    for path in groupby_sources():
-        kernels |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", open(path).read()))
+    kernels = support.global_kernels_of("groupby")
     assert kernels == {INIT_KERNEL, AGG_KERNEL}, kernels
-    me = open(__file__).read()
-    gpu_part = me[me.index("# GPU\n"):]
-    for const in ("INIT_KERNEL", "AGG_KERNEL"):
-        assert re.search(rf"assert [^\n]*\b{const}\b", gpu_part), f"no GPU case asserts {const} from the launch record"
+    support.check_gpu_part_asserts(__file__, "INIT_KERNEL", "AGG_KERNEL")
 
 
 def test_groupby_sources_read_no_flag_bits():
-    assert groupby_sources()
-    for path in groupby_sources():
-        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(path).read(), flags=re.S)
-        assert not re.search(r"flags\s*&", text), f"{os.path.relpath(path, ROOT)} tests a kernel_flags bit"
+    support.check_sources_read_no_flag_bits("groupby")
 
 
 def gpu_shapes():
@@ -296,25 +212,6 @@ def test_same_buffer_recipe_is_not_vacuous():
 # ---------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def eng():
-    from shared_simd_scan_amd import ScanEngine
-
-    e = ScanEngine(0)
-    yield e
-    e.close()
-
-
-def record(L, eng):
-    return parse_record((L.mi355_ctx_last_launch(eng._ctx) or b"").decode())
-
-
-def upload(O, values, c):
-    import torch
-
-    return torch.from_numpy(O.pack(np.ascontiguousarray(values, dtype=np.uint32), c)).cuda()
-
 
 class Bench:
     """one engine, the uploaded columns of a width pair, a guarded output that is refilled with 0xEE before every call"""

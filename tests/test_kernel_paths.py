@@ -734,6 +734,7 @@ def check_select(L, eng, packed, vals, n, c, op, a, capacity_kind, first_row=100
         assert (ids.t[ids.front + 8 * k: ids.front + 8 * cap].cpu().numpy() == SENTINEL).all(), "ids written beyond the count"
 
 
+# differs from support.L: a missing library is an error here, it is not built
 @pytest.fixture(scope="module")
 def L():
     from shared_simd_scan_amd import lib

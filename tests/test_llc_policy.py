@@ -114,6 +114,7 @@ def run_case(L, O, c, mode, n, options, divisors):
                 eng.close()
 
 
+# differs from support.L: a missing library is an error here, it is not built
 @pytest.fixture(scope="module")
 def L():
     from shared_simd_scan_amd import lib

@@ -17,20 +17,16 @@ the smallest that reach one lane, one partial tile, one full tile, a full tile p
 """
 import ctypes as C
 import functools
-import glob
 import os
-import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import support
+from support import L, RecordingLib, eng, header_macro, hostile_pack, plain_pack, record  # noqa: F401  (L, eng: fixtures)
 from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-LOOKUP_DIR = os.path.join(ROOT, "shared_simd_scan_amd", "csrc", "lookup")
 HEADER = "mi355_lookup.h"
 E_INVALID = -1
 
@@ -39,13 +35,7 @@ LDS_KERNEL = "lookup_lds_kernel"
 GLOBAL_KERNEL = "lookup_global_kernel"
 
 
-def header_macro(name):
-    m = re.search(rf"^#define {name}\s+(\d+)", open(os.path.join(INCLUDE, HEADER)).read(), flags=re.M)
-    assert m, name
-    return int(m.group(1))
-
-
-LDS_MAX = header_macro("MI355_LOOKUP_LDS_MAX_BYTES")
+LDS_MAX = header_macro(HEADER, "MI355_LOOKUP_LDS_MAX_BYTES")
 R = 2048  # rows per tile: 64 lanes x 32 rows
 
 
@@ -165,47 +155,23 @@ def payload(n, c):
 # CPU
 # ---------------------------------------------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def L():
-    from shared_simd_scan_amd import build, lib
-
-    if not os.path.exists(build.LIB_PATH):
-        build.build()
-    return lib()
-
-
-def declared(header):
-    text = open(os.path.join(INCLUDE, header)).read()
-    return sorted(set(re.findall(r"^MI355_API [^;(]*?\b(mi355_\w+)\(", text, flags=re.M)))
-
-
 def test_lookup_header_is_plain_c99():
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c", os.path.join(INCLUDE, HEADER)],
-                   check=True)
+    support.check_header_is_plain_c99(HEADER)
 
 
 def test_lookup_header_declares_what_python_binds(L):
     from shared_simd_scan_amd import _capi
 
-    names = declared(HEADER)
-    assert names == sorted(s[0] for s in _capi.LOOKUP_SYMBOLS) and names == ["mi355_lookup_dev", "mi355_lookup_kernel"]
-    sigs = dict((s[0], s[2]) for s in _capi.LOOKUP_SYMBOLS)
-    for name in names:
-        assert hasattr(L, name), name
-        assert getattr(L, name).argtypes == sigs[name]  # lib() applied the list
-    for other in ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h"):
-        assert not set(names) & set(declared(other)), other
-        assert HEADER not in open(os.path.join(INCLUDE, other)).read(), f"{other} includes {HEADER}"
-    assert not set(names) & {s[0] for s in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS}
+    names, sigs = support.check_header_binds(L, HEADER, _capi.LOOKUP_SYMBOLS, ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h"),
+                                             _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS)
+    assert names == ["mi355_lookup_dev", "mi355_lookup_kernel"]
     sig = sigs["mi355_lookup_dev"]
     assert sig[2] is C.c_uint64 and sig[3] is C.c_uint and sig[5] is C.c_uint64 and sig[6] is C.c_uint and sig[7] is C.c_uint32 and len(sig) == 9
     assert sigs["mi355_lookup_kernel"] == [C.c_uint, C.c_uint64, C.c_uint] and L.mi355_lookup_kernel.restype is C.c_char_p
 
 
 def test_lookup_header_carries_its_capture_verdict():
-    text = open(os.path.join(INCLUDE, HEADER)).read()
-    assert re.search(r"graph capture: capturable\b", text)
-    assert re.search(r"read at every replay", text)
+    support.check_capture_verdict(HEADER, r"read at every replay")
 
 
 def test_header_limit_is_the_budget_it_describes(L):
@@ -259,50 +225,13 @@ def test_width_cases_reach_both_tiers(L):
         assert L.mi355_lookup_kernel(c, T, ct).decode() == want_family(c, ct, T), case
 
 
-class _RecordingLib:
-    """stand-in for libmi355scan.so: converts the arguments through the real argtypes (as ctypes would) and records them; the
-    buffer-size arithmetic goes to the real library"""
-
-    def __init__(self, real):
-        from shared_simd_scan_amd import _capi
-
-        self.calls = []
-        self.mi355_compressed_buffer_size = real.mi355_compressed_buffer_size
-        self._sig = {name: args for name, _, args in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS + _capi.LOOKUP_SYMBOLS}
-
-    def __getattr__(self, name):
-        argtypes = self._sig[name]
-
-        def call(*args):
-            assert len(args) == len(argtypes), name
-            conv = []
-            for t, a in zip(argtypes, args):
-                if t in (C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_int, C.c_uint) and isinstance(a, int):
-                    a = t(a).value
-                conv.append(a)
-            self.calls.append((name, conv))
-            return 0
-
-        return call
-
-
+# differs from support.fake: the buffer-size arithmetic goes to the real library, and lookup's result is a PackedColumn
 @pytest.fixture
 def fake(monkeypatch, L):
-    import torch
-
     from shared_simd_scan_amd import engine
 
-    rec = _RecordingLib(L)
-    monkeypatch.setattr(engine, "lib", lambda: rec)
-    monkeypatch.setattr(engine, "check", lambda rc: None)
     monkeypatch.setattr(engine, "PackedColumn", lambda data, n, c: types.SimpleNamespace(data=data, n=int(n), c=int(c)))  # (the real one wants a device tensor)
-    eng = object.__new__(engine.ScanEngine)
-    eng._ctx, eng._dev = None, torch.device("cpu")
-
-    def col(c, n=1000):
-        return types.SimpleNamespace(data=torch.zeros(64, dtype=torch.uint8), n=n, c=c)
-
-    return eng, rec, col
+    return support.fake_engine(monkeypatch, RecordingLib(L))
 
 
 def test_lookup_wrapper_passes_what_the_abi_takes(fake, L):
@@ -349,28 +278,18 @@ def test_lookup_entry_point_fails_loudly_without_a_gpu(L):
     assert rc != 0 and L.mi355_last_error()
 
 
-def lookup_sources():
-    return sorted(glob.glob(os.path.join(LOOKUP_DIR, "*.hpp")) + glob.glob(os.path.join(LOOKUP_DIR, "*.hip")))
-
-
 def test_every_lookup_kernel_has_a_case():
     """every __global__ under csrc/lookup/ is asserted from the launch record by a GPU case of this file, and the file names no
     kernel that does not exist"""
-    kernels = set()
-    for path in lookup_sources():
-        kernels |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", open(path).read()))
+    kernels = support.global_kernels_of("lookup")
     assert kernels == {LDS_KERNEL, GLOBAL_KERNEL}, kernels
-    me = open(__file__).read()
-    gpu_part = me[me.index("# GPU\n"):]
-    assert re.search(r"assert [^\n]*\bwant_family\(", gpu_part), "no GPU case asserts the predicted kernel from the launch record"
+    support.check_gpu_part_asserts(__file__, r"want_family\(")  # (not the constants: the GPU cases assert the predicted kernel)
     assert {want_family(*case) for case in WIDTH_CASES} == kernels
 
 
 def test_lookup_sources_read_no_flag_bits():
-    assert [os.path.basename(p) for p in lookup_sources()] == ["lookup.hip", "lookup.hpp"]
-    for path in lookup_sources():
-        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(path).read(), flags=re.S)
-        assert not re.search(r"flags\s*&", text), f"{os.path.relpath(path, ROOT)} tests a kernel_flags bit"
+    assert [os.path.basename(p) for p in support.feature_sources("lookup")] == ["lookup.hip", "lookup.hpp"]
+    support.check_sources_read_no_flag_bits("lookup")
 
 
 def gpu_shapes():
@@ -497,44 +416,6 @@ def test_capture_data_is_not_vacuous(case):
 # ---------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def eng():
-    from shared_simd_scan_amd import ScanEngine
-
-    e = ScanEngine(0)
-    yield e
-    e.close()
-
-
-def record(L, eng):
-    return parse_record((L.mi355_ctx_last_launch(eng._ctx) or b"").decode())
-
-
-def hostile_pack(O, values, c, offset=0):
-    """the oracle's packed image of `values` in hostile surroundings -> device tensor (a view at `offset` bytes, a multiple of 4,
-    behind a 16-byte boundary): ones in the bits behind the last value and in every byte of the pad, 0xFF in front of the view"""
-    import torch
-
-    n = len(values)
-    img = O.pack(np.ascontiguousarray(values, dtype=np.uint32), c).copy()
-    nb = payload(n, c)
-    if (n * c) % 8:
-        img[nb - 1] |= (0xFF << ((n * c) % 8)) & 0xFF
-    img[nb:] = 0xFF
-    buf = torch.full((16 + offset + len(img),), 0xFF, dtype=torch.uint8, device="cuda")
-    buf = buf[(-buf.data_ptr()) % 16:]
-    buf[offset: offset + len(img)] = torch.from_numpy(img).cuda()
-    view = buf[offset: offset + len(img)]
-    assert view.data_ptr() % 16 == offset % 16
-    return view
-
-
-def plain_pack(O, values, c):
-    import torch
-
-    return torch.from_numpy(O.pack(np.ascontiguousarray(values, dtype=np.uint32), c)).cuda()
-
 
 class Look:
     """one engine, an uploaded column and table (both in hostile surroundings), a guarded output refilled with 0xEE before every call"""

@@ -134,6 +134,7 @@ def test_keys32_is_key32_over_the_list(c):
 
 # ---- every wrapper converts its constants before ctypes sees them ----------------------------------------------------
 
+# differs from support.RecordingLib: the key lists are read through their pointers, and args() finds a call by name
 class _RecordingLib:
     """stand-in for libmi355scan.so: each call converts its arguments through the real argtypes (as ctypes would) and
     records them; the key lists are read through their pointers"""

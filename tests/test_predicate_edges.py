@@ -104,6 +104,7 @@ def edge_values(c, n, seed):
     return v.astype(np.uint32)
 
 
+# differs from support.L: a missing library is an error here, it is not built
 @pytest.fixture(scope="module")
 def L():
     from shared_simd_scan_amd import lib
@@ -111,6 +112,7 @@ def L():
     return lib()
 
 
+# differs from support.eng: says why when there is no GPU, takes the current device, is never closed
 @pytest.fixture(scope="module")
 def eng():
     import torch

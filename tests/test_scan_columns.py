@@ -12,18 +12,15 @@ engine output.  Output buffers sit inside 0xEE guard bytes (test_kernel_paths.Gu
 import ctypes as C
 import functools
 import operator
-import os
-import re
-import subprocess
-import types
 
 import numpy as np
 import pytest
 
-from test_kernel_paths import SENTINEL, Guarded, packbits, parse_record
+import support
+from support import L, eng, fake, record  # noqa: F401  (L, eng, fake: fixtures)
+from test_kernel_paths import SENTINEL, Guarded, packbits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
+HEADER = "mi355_columns.h"
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 E_INVALID = -1
 OPS = ["==", "!=", "<", "<=", ">", ">=", "between", "not_between"]
@@ -66,40 +63,19 @@ def py_pred(d, op, a, b):
 # CPU
 # ---------------------------------------------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def L():
-    from shared_simd_scan_amd import build, lib
-
-    if not os.path.exists(build.LIB_PATH):
-        build.build()
-    return lib()
-
-
-def declared(header):
-    text = open(os.path.join(INCLUDE, header)).read()
-    return sorted(set(re.findall(r"^MI355_API [^;(]*?\b(mi355_\w+)\(", text, flags=re.M)))
-
-
 def test_columns_header_is_plain_c99():
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c",
-                    os.path.join(INCLUDE, "mi355_columns.h")], check=True)
+    support.check_header_is_plain_c99(HEADER)
 
 
 def test_columns_header_declares_what_python_binds(L):
     from shared_simd_scan_amd import _capi
 
-    names = declared("mi355_columns.h")
-    assert names == sorted(s[0] for s in _capi.COLUMN_SYMBOLS) and "mi355_scan_columns_dev" in names
-    for name in names:
-        assert hasattr(L, name), name
-        assert getattr(L, name).argtypes == dict((s[0], s[2]) for s in _capi.COLUMN_SYMBOLS)[name]  # lib() applied the list
-    assert not set(names) & set(declared("mi355_scan.h"))
-    assert not set(names) & {s[0] for s in _capi.SYMBOLS}
+    names, sigs = support.check_header_binds(L, HEADER, _capi.COLUMN_SYMBOLS, ("mi355_scan.h",), _capi.SYMBOLS)
+    assert "mi355_scan_columns_dev" in names
 
 
 def test_columns_header_carries_its_capture_verdict():
-    text = open(os.path.join(INCLUDE, "mi355_columns.h")).read()
-    assert re.search(r"graph capture: capturable\b", text)
+    support.check_capture_verdict(HEADER)
 
 
 def test_difference_constants_are_int64_arguments():
@@ -137,49 +113,6 @@ def test_clamp_diff_keeps_every_comparison(c1, c2):
             for d in difference_edges(c1, c2):
                 for op in OPS[6:]:
                     assert py_pred(d, op, clamp_diff(a), clamp_diff(b)) == py_pred(d, op, a, b), (c1, c2, d, op, a, b)
-
-
-class _RecordingLib:
-    """stand-in for libmi355scan.so: converts the arguments through the real argtypes (as ctypes would) and records them"""
-
-    def __init__(self):
-        from shared_simd_scan_amd import _capi
-
-        self.calls = []
-        self._sig = {name: args for name, _, args in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS}
-
-    def __getattr__(self, name):
-        argtypes = self._sig[name]
-
-        def call(*args):
-            assert len(args) == len(argtypes), name
-            conv = []
-            for t, a in zip(argtypes, args):
-                if t in (C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_int, C.c_uint) and isinstance(a, int):
-                    a = t(a).value
-                conv.append(a)
-            self.calls.append((name, conv))
-            return 0
-
-        return call
-
-
-@pytest.fixture
-def fake(monkeypatch):
-    import torch
-
-    from shared_simd_scan_amd import engine
-
-    rec = _RecordingLib()
-    monkeypatch.setattr(engine, "lib", lambda: rec)
-    monkeypatch.setattr(engine, "check", lambda rc: None)
-    eng = object.__new__(engine.ScanEngine)
-    eng._ctx, eng._dev = None, torch.device("cpu")
-
-    def col(c, n=1000):
-        return types.SimpleNamespace(data=torch.zeros(64, dtype=torch.uint8), n=n, c=c)
-
-    return eng, rec, col
 
 
 def test_scan_columns_wrapper_passes_what_the_abi_takes(fake):
@@ -309,19 +242,6 @@ class Bench:
         assert int(self.hits.fetch().view(np.uint64)[0]) == int(want.sum()), tag
         if mask_bits is not None and not inplace:
             assert np.array_equal(mask.cpu().numpy(), packbits(mask_bits)), ("mask written", tag)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from shared_simd_scan_amd import ScanEngine
-
-    e = ScanEngine(0)
-    yield e
-    e.close()
-
-
-def record(L, eng):
-    return parse_record((L.mi355_ctx_last_launch(eng._ctx) or b"").decode())
 
 
 @pytest.mark.parametrize("pair", PAIRS + EXTRA, ids=pid)

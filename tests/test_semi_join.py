@@ -16,20 +16,15 @@ tile plus one row and many tiles with a ragged tail.
 """
 import ctypes as C
 import functools
-import glob
-import os
-import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import support
+from support import L, eng, fake, header_macro, record, upload  # noqa: F401  (L, eng, fake: fixtures)
 from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-SEMIJOIN_DIR = os.path.join(ROOT, "shared_simd_scan_amd", "csrc", "semijoin")
 HEADER = "mi355_semijoin.h"
 E_INVALID = -1
 
@@ -38,13 +33,7 @@ LDS_KERNEL = "semijoin_lds_kernel"
 GLOBAL_KERNEL = "semijoin_global_kernel"
 
 
-def header_macro(name):
-    m = re.search(rf"^#define {name}\s+(\d+)", open(os.path.join(INCLUDE, HEADER)).read(), flags=re.M)
-    assert m, name
-    return int(m.group(1))
-
-
-LDS_MAX = header_macro("MI355_SEMIJOIN_LDS_MAX_BITS")
+LDS_MAX = header_macro(HEADER, "MI355_SEMIJOIN_LDS_MAX_BITS")
 
 N_BIG = 8192 * 9 + 1237  # 74965: nine tiles of 8192 rows (eighteen of 4096) and a ragged one; not a multiple of 8
 SIZES = [1, 13, 509, 4096, 4097, 8192, 8193, N_BIG]
@@ -190,47 +179,23 @@ def capture_data(c, m):
 # CPU
 # ---------------------------------------------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def L():
-    from shared_simd_scan_amd import build, lib
-
-    if not os.path.exists(build.LIB_PATH):
-        build.build()
-    return lib()
-
-
-def declared(header):
-    text = open(os.path.join(INCLUDE, header)).read()
-    return sorted(set(re.findall(r"^MI355_API [^;(]*?\b(mi355_\w+)\(", text, flags=re.M)))
-
-
 def test_semijoin_header_is_plain_c99():
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c", os.path.join(INCLUDE, HEADER)],
-                   check=True)
+    support.check_header_is_plain_c99(HEADER)
 
 
 def test_semijoin_header_declares_what_python_binds(L):
     from shared_simd_scan_amd import _capi
 
-    names = declared(HEADER)
-    assert names == sorted(s[0] for s in _capi.SEMIJOIN_SYMBOLS) and names == ["mi355_semijoin_dev", "mi355_semijoin_kernel"]
-    sigs = dict((s[0], s[2]) for s in _capi.SEMIJOIN_SYMBOLS)
-    for name in names:
-        assert hasattr(L, name), name
-        assert getattr(L, name).argtypes == sigs[name]  # lib() applied the list
-    for other in ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h"):
-        assert not set(names) & set(declared(other)), other
-        assert HEADER not in open(os.path.join(INCLUDE, other)).read(), f"{other} includes {HEADER}"
-    assert not set(names) & {s[0] for s in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS}
+    names, sigs = support.check_header_binds(L, HEADER, _capi.SEMIJOIN_SYMBOLS, ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h"),
+                                             _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS)
+    assert names == ["mi355_semijoin_dev", "mi355_semijoin_kernel"]
     sig = sigs["mi355_semijoin_dev"]
     assert sig[2] is C.c_uint64 and sig[3] is C.c_uint and sig[5] is C.c_uint64 and sig[6] is C.c_int and len(sig) == 10
     assert sigs["mi355_semijoin_kernel"] == [C.c_uint, C.c_uint64] and L.mi355_semijoin_kernel.restype is C.c_char_p
 
 
 def test_semijoin_header_carries_its_capture_verdict():
-    text = open(os.path.join(INCLUDE, HEADER)).read()
-    assert re.search(r"graph capture: capturable\b", text)
-    assert re.search(r"read at every replay", text)
+    support.check_capture_verdict(HEADER, r"read at every replay")
 
 
 def test_kernel_choice_at_the_boundaries(L):
@@ -261,49 +226,6 @@ def test_width_cases_reach_both_tiers(L):
     assert {c for (c, m), f in fam.items() if f == LDS_KERNEL} == set(range(1, 33))
     assert {c for (c, m), f in fam.items() if f == GLOBAL_KERNEL} == set(range(20, 33))
     assert fam[(20, 1 << 19)] == LDS_KERNEL and fam[(32, 1 << 19)] == LDS_KERNEL
-
-
-class _RecordingLib:
-    """stand-in for libmi355scan.so: converts the arguments through the real argtypes (as ctypes would) and records them"""
-
-    def __init__(self):
-        from shared_simd_scan_amd import _capi
-
-        self.calls = []
-        self._sig = {name: args for name, _, args in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS}
-
-    def __getattr__(self, name):
-        argtypes = self._sig[name]
-
-        def call(*args):
-            assert len(args) == len(argtypes), name
-            conv = []
-            for t, a in zip(argtypes, args):
-                if t in (C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_int, C.c_uint) and isinstance(a, int):
-                    a = t(a).value
-                conv.append(a)
-            self.calls.append((name, conv))
-            return 0
-
-        return call
-
-
-@pytest.fixture
-def fake(monkeypatch):
-    import torch
-
-    from shared_simd_scan_amd import engine
-
-    rec = _RecordingLib()
-    monkeypatch.setattr(engine, "lib", lambda: rec)
-    monkeypatch.setattr(engine, "check", lambda rc: None)
-    eng = object.__new__(engine.ScanEngine)
-    eng._ctx, eng._dev = None, torch.device("cpu")
-
-    def col(c, n=1000):
-        return types.SimpleNamespace(data=torch.zeros(64, dtype=torch.uint8), n=n, c=c)
-
-    return eng, rec, col
 
 
 def test_semi_join_wrapper_passes_what_the_abi_takes(fake):
@@ -364,28 +286,16 @@ def test_semijoin_entry_point_fails_loudly_without_a_gpu(L):
     assert rc != 0 and L.mi355_last_error()
 
 
-def semijoin_sources():
-    return sorted(glob.glob(os.path.join(SEMIJOIN_DIR, "*.hpp")) + glob.glob(os.path.join(SEMIJOIN_DIR, "*.hip")))
-
-
 def test_every_semijoin_kernel_has_a_case():
     """every __global__ under csrc/semijoin/ is asserted from the launch record by a GPU case of this file, and the file names
     no kernel that does not exist"""
-    kernels = set()
-    for path in semijoin_sources():
-        kernels |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", open(path).read()))
+    kernels = support.global_kernels_of("semijoin")
     assert kernels == {LDS_KERNEL, GLOBAL_KERNEL}, kernels
-    me = open(__file__).read()
-    gpu_part = me[me.index("# GPU\n"):]
-    for const in ("LDS_KERNEL", "GLOBAL_KERNEL"):
-        assert re.search(rf"assert [^\n]*\b{const}\b", gpu_part), f"no GPU case asserts {const} from the launch record"
+    support.check_gpu_part_asserts(__file__, "LDS_KERNEL", "GLOBAL_KERNEL")
 
 
 def test_semijoin_sources_read_no_flag_bits():
-    assert semijoin_sources()
-    for path in semijoin_sources():
-        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(path).read(), flags=re.S)
-        assert not re.search(r"flags\s*&", text), f"{os.path.relpath(path, ROOT)} tests a kernel_flags bit"
+    support.check_sources_read_no_flag_bits("semijoin")
 
 
 def test_header_limit_is_the_kernels(L):
@@ -496,25 +406,6 @@ def test_empty_set_expectation():
 # ---------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def eng():
-    from shared_simd_scan_amd import ScanEngine
-
-    e = ScanEngine(0)
-    yield e
-    e.close()
-
-
-def record(L, eng):
-    return parse_record((L.mi355_ctx_last_launch(eng._ctx) or b"").decode())
-
-
-def upload(O, values, c):
-    import torch
-
-    return torch.from_numpy(O.pack(np.ascontiguousarray(values, dtype=np.uint32), c)).cuda()
-
 
 def family(L, c, m):
     return L.mi355_semijoin_kernel(c, m).decode()

@@ -75,6 +75,7 @@ def np_pred(v, op, a, b=0):
     return inside if op == "between" else ~inside
 
 
+# differs from support.L: a missing library is an error here, it is not built
 @pytest.fixture(scope="module")
 def L():
     from shared_simd_scan_amd import lib
@@ -82,6 +83,7 @@ def L():
     return lib()
 
 
+# differs from support.eng: says why when there is no GPU, takes the current device, is never closed
 @pytest.fixture(scope="module")
 def eng():
     import torch

@@ -1,4 +1,4 @@
-"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h, include/mi355_semijoin.h, include/mi355_lookup.h and include/mi355_compact.h.  No compute happens in Python; a missing library is an error."""
+"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h, include/mi355_semijoin.h, include/mi355_lookup.h, include/mi355_compact.h and include/mi355_arith.h.  No compute happens in Python; a missing library is an error."""
 from __future__ import annotations
 
 import ctypes as C
@@ -111,6 +111,12 @@ COMPACT_SYMBOLS = [
     ("mi355_compact_kernel", C.c_char_p, [C.c_uint]),
 ]
 
+# every symbol include/mi355_arith.h declares (a packed column computed row by row from two others): bound by lib() as well
+ARITH_SYMBOLS = [
+    ("mi355_arith_dev", _int, [_vp, _int, _vp, C.c_uint, _vp, C.c_uint, _u64, _i32, _i32, C.c_int64, C.c_uint, _u32, _vp, _vp]),
+    ("mi355_arith_kernel", C.c_char_p, [_int, C.c_uint, C.c_uint, _i32, _i32, C.c_int64, C.c_uint]),
+]
+
 
 class Predicate(C.Structure):
     """mi355_predicate: one comparison `v OP a [, b]` of a shared where-scan"""
@@ -130,7 +136,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the HIP extension is not built (run `python -m shared_simd_scan_amd.build`). "
                 "There is no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS + LOOKUP_SYMBOLS + COMPACT_SYMBOLS:
+        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS + LOOKUP_SYMBOLS + COMPACT_SYMBOLS + ARITH_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export what the header declares
             fn.restype = res
             fn.argtypes = args

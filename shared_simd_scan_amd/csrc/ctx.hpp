@@ -1,6 +1,7 @@
 // ctx.hpp -- the context object behind include/mi355_scan.h and what every host-side translation unit of libmi355scan.so
 // shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip, groupby/group_aggregate.hip,
-// semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith.hip and arith/arith_kernels.hip):
+// semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith.hip, arith/arith_kernels.hip and
+// groupby_wide/group_aggregate_wide.hip):
 // error reporting, the entry prologue, the context's buffers.
 #pragma once
 
@@ -156,7 +157,7 @@ int upload_list(mi355_ctx *ctx, const void *src, size_t elem_bytes, unsigned P, 
 // CUs the persistent grids are sized for (option "grid_cus")
 inline int grid_cus(const mi355_ctx *ctx) { return ctx->grid_cus > 0 ? ctx->grid_cus : ctx->num_cus; }
 
-// What a launcher outside the width groups (groupby/, semijoin/, lookup/, compact/, arith/) takes from its context; the groups' LaunchReq has the
+// What a launcher outside the width groups (groupby/, groupby_wide/, semijoin/, lookup/, compact/, arith/) takes from its context; the groups' LaunchReq has the
 // same five among its fields (capi.hip fill_common).
 struct LaunchEnv {
     hipStream_t stream;

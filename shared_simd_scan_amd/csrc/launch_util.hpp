@@ -1,6 +1,6 @@
 // launch_util.hpp -- the host-side launch helpers that the translation units with a launcher share, one copy of each: capi.hip,
 // extras.hip, the three group units (width_group.hip, predicates/where_group.hip, predicates/columns_group.hip) and the feature
-// units (groupby/group_aggregate.hip, semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith_kernels.hip).  No device code.
+// units (groupby/group_aggregate.hip, groupby_wide/group_aggregate_wide.hip, semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith_kernels.hip).  No device code.
 #pragma once
 
 #include <atomic>

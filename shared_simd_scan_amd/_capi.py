@@ -1,4 +1,4 @@
-"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h, include/mi355_semijoin.h, include/mi355_lookup.h, include/mi355_compact.h, include/mi355_arith.h and include/mi355_groupby_wide.h.  No compute happens in Python; a missing library is an error."""
+"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h, include/mi355_semijoin.h, include/mi355_lookup.h, include/mi355_compact.h, include/mi355_arith.h, include/mi355_groupby_wide.h and include/mi355_topk.h.  No compute happens in Python; a missing library is an error."""
 from __future__ import annotations
 
 import ctypes as C
@@ -123,6 +123,12 @@ GROUP_WIDE_SYMBOLS = [
     ("mi355_group_wide_front_slots", _u32, [C.c_uint, C.c_uint]),
 ]
 
+# every symbol include/mi355_topk.h declares (the k largest or smallest rows of a column, as a bitmap): bound by lib() as well
+TOPK_SYMBOLS = [
+    ("mi355_top_k_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _u64, _int, _vp, _vp]),
+    ("mi355_top_k_passes", C.c_uint, [C.c_uint]),
+]
+
 
 class Predicate(C.Structure):
     """mi355_predicate: one comparison `v OP a [, b]` of a shared where-scan"""
@@ -142,7 +148,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the HIP extension is not built (run `python -m shared_simd_scan_amd.build`). "
                 "There is no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS + LOOKUP_SYMBOLS + COMPACT_SYMBOLS + ARITH_SYMBOLS + GROUP_WIDE_SYMBOLS:
+        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS + LOOKUP_SYMBOLS + COMPACT_SYMBOLS + ARITH_SYMBOLS + GROUP_WIDE_SYMBOLS + TOPK_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the library does not export what the header declares
             fn.restype = res
             fn.argtypes = args

@@ -1,7 +1,7 @@
 // ctx.hpp -- the context object behind include/mi355_scan.h and what every host-side translation unit of libmi355scan.so
 // shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip, groupby/group_aggregate.hip,
-// semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith.hip, arith/arith_kernels.hip and
-// groupby_wide/group_aggregate_wide.hip):
+// semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith.hip, arith/arith_kernels.hip,
+// groupby_wide/group_aggregate_wide.hip and topk/top_k.hip):
 // error reporting, the entry prologue, the context's buffers.
 #pragma once
 
@@ -59,7 +59,7 @@ struct mi355_ctx {
     bool key_used[mi355::kKeySlots] = {};
     int key_next = 0;
     hipEvent_t order_event = nullptr;           // mi355_ctx_set_stream: new stream waits for the old one
-    unsigned long long *rowid_ws = nullptr;     // chunk counts of mi355_bitmap_to_rowids_dev / mi355_scan_select_dev / mi355_compact_dev
+    unsigned long long *rowid_ws = nullptr;     // chunk counts of mi355_bitmap_to_rowids_dev / mi355_scan_select_dev / mi355_compact_dev / mi355_top_k_dev
     size_t rowid_ws_entries = 0;
     // Graph capture: a captured memset / kernel node keeps the address of the workspace or pool slot it was recorded with.  A
     // buffer used under capture is marked; when it has to grow later it is retired (freed in mi355_ctx_destroy) instead of freed,
@@ -157,7 +157,7 @@ int upload_list(mi355_ctx *ctx, const void *src, size_t elem_bytes, unsigned P, 
 // CUs the persistent grids are sized for (option "grid_cus")
 inline int grid_cus(const mi355_ctx *ctx) { return ctx->grid_cus > 0 ? ctx->grid_cus : ctx->num_cus; }
 
-// What a launcher outside the width groups (groupby/, groupby_wide/, semijoin/, lookup/, compact/, arith/) takes from its context; the groups' LaunchReq has the
+// What a launcher outside the width groups (groupby/, groupby_wide/, semijoin/, lookup/, compact/, arith/, topk/) takes from its context; the groups' LaunchReq has the
 // same five among its fields (capi.hip fill_common).
 struct LaunchEnv {
     hipStream_t stream;

@@ -3,15 +3,15 @@
 // packed in and packed out -- the composite key of GROUP BY a, b, the product under sum(price * discount), the difference
 // that histogram / lookup / group_aggregate consume.  gfx950 only; part of libmi355scan.so through arith/arith.hip.
 //
-// Pipeline.  lookup_body's (lookup/lookup.hpp), with scan_columns_kernel's second input: a wave owns tiles of 64 x 32
+// Pipeline.  The run-time-width tile stream of kernels/rt_column.hpp, twice in and packed out: a wave owns tiles of 64 x 32
 // consecutive rows, lane l rows [32 l, 32 l + 32) of BOTH columns.  The kernels are templates of the OUTPUT width CO only
-// (2 x 32 instantiations): a lane's 32 results are exactly CO dwords, assembled by insert<CO, K> and stored at byte
+// (2 x 32 instantiations): a lane's 32 results are exactly CO dwords, assembled by rt_insert<CO, K> and stored at byte
 // 4 CO lane of the tile's 256 CO output bytes.  Both input widths are wave-uniform run-time numbers: both tiles travel by
-// non-temporal LDS-DMA, stay in LDS and are decoded from there (columns_lds_value), so a wave has two alternating images of
-// EACH column -- the next tiles land in one pair while the other is decoded.  A full tile's dwords leave one tile late, in
-// front of the next DMA (lookup_store); the ragged tile writes exactly the bytes it owns (lookup_store_tail).  insert, the
-// decode, the two stores and the image size are lookup.hpp's, not copies.  The same buffer as both inputs fills both image
-// sets like any other pair.
+// non-temporal LDS-DMA, stay in LDS and are decoded from there (columns_lds_value), so a wave has two
+// alternating images of EACH column -- the next tiles land in one pair while the other is decoded.  A full tile's dwords leave
+// one tile late, in front of the next DMA (rt_store); the ragged tile writes exactly the bytes it owns (rt_store_tail).
+// The geometry, the decode, rt_insert, the two stores and wave_sum64 are rt_column.hpp's, not copies; the DMA loop is the kernels' own.  The same buffer as both
+// inputs fills both image sets like any other pair.
 //
 // Arithmetic.  The host (arith.hip, arith_plan) has bounded r over ALL x < 2^c1, y < 2^c2 in 128 bits:
 //   arith_exact_kernel    [lo, hi] lies within [0, 2^CO - 1]: no row can be out of range -- rows >= n of the ragged tile
@@ -29,8 +29,7 @@
 #pragma once
 
 #include "../kernels.hpp"
-#include "../lookup/lookup.hpp" // insert, lookup_store, lookup_store_tail, lookup_image: the packed-out half of the pipeline
-#include "../predicates/columns.hpp" // columns_lds_value: a value of run-time width out of LDS
+#include "../kernels/rt_column.hpp" // the tile stream of a column of run-time width, and the packed-out half
 
 namespace mi355 {
 
@@ -50,7 +49,7 @@ struct ArithArgs {
 };
 
 // a wave's images: two of each column
-constexpr uint32_t arith_wave_lds(uint32_t c1, uint32_t c2) { return 2u * lookup_image(c1) + 2u * lookup_image(c2); }
+constexpr uint32_t arith_wave_lds(uint32_t c1, uint32_t c2) { return 2u * rt_image(c1) + 2u * rt_image(c2); }
 // + 16: the dword behind the last lane's run is read (and not used)
 constexpr uint32_t arith_block_lds(uint32_t c1, uint32_t c2) { return kWavesPerBlock * arith_wave_lds(c1, c2) + 16u; }
 static_assert(arith_block_lds(32, 32) <= kCuLdsBytes, "LDS budget");
@@ -95,46 +94,48 @@ __device__ __forceinline__ void arith_rows(const ArithArgs &q, const uint8_t *ba
         // 64-bit wrap-around is exact under the range rule; (uint64)r < 2^CO also sends a negative r to `miss`
         const uint64_t t = arith_one<MODE, uint64_t>((uint64_t)(int64_t)q.a, (uint64_t)(int64_t)q.b, (uint64_t)q.k, x, y);
         const bool in = (t >> CO) == 0;
-        insert<CO, K>(res, in ? (uint32_t)t : q.miss);
+        rt_insert<CO, K>(res, in ? (uint32_t)t : q.miss);
         bad |= in ? 0u : (1u << K);
     } else {
         // the true result lies in [0, 2^CO) within [0, 2^32): 32-bit wrap-around yields it
-        insert<CO, K>(res, arith_one<MODE, uint32_t>((uint32_t)q.a, (uint32_t)q.b, (uint32_t)q.k, x, y));
+        rt_insert<CO, K>(res, arith_one<MODE, uint32_t>((uint32_t)q.a, (uint32_t)q.b, (uint32_t)q.k, x, y));
     }
-    if constexpr (K + 1 < kLookupVpl) arith_rows<CO, CHECKED, MODE, K + 1>(q, base1, c1, vmask1, base2, c2, vmask2, res, bad);
+    if constexpr (K + 1 < kRtVpl) arith_rows<CO, CHECKED, MODE, K + 1>(q, base1, c1, vmask1, base2, c2, vmask2, res, bad);
 }
 
 template <int CO, bool CHECKED> __device__ __forceinline__ void arith_body(const ArithArgs &a)
 {
-    constexpr int VPL = kLookupVpl;
+    constexpr int VPL = kRtVpl;
     constexpr int AUX = 2; // both columns are streamed once: non-temporal DMA
-    constexpr uint32_t OUT_TILE = 64u * VPL / 8u * CO; // output bytes of a tile
+    constexpr uint32_t OUT_TILE = rt_tile_bytes(CO); // output bytes of a tile
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t c1 = a.c1, c2 = a.c2;
-    const uint32_t tile_bytes1 = 64u * VPL / 8u * c1, tile_bytes2 = 64u * VPL / 8u * c2; // multiples of 256
-    const uint32_t image1 = lookup_image(c1), image2 = lookup_image(c2);
+    const uint32_t tile_bytes1 = rt_tile_bytes(c1), tile_bytes2 = rt_tile_bytes(c2); // multiples of 256
+    const uint32_t image1 = rt_image(c1), image2 = rt_image(c2);
     uint8_t *cur1 = mi355_dyn_lds + (uint32_t)wave * arith_wave_lds(c1, c2); // the images being decoded ...
     uint8_t *nxt1 = cur1 + image1;                                           // ... and where the next tiles land
     uint8_t *cur2 = cur1 + 2u * image1;
     uint8_t *nxt2 = cur2 + image2;
-    const uint32_t vmask1 = c1 >= 32 ? 0xffffffffu : ((1u << c1) - 1u), vmask2 = c2 >= 32 ? 0xffffffffu : ((1u << c2) - 1u);
+    const uint32_t vmask1 = rt_vmask(c1), vmask2 = rt_vmask(c2);
 
     const uint64_t n = a.n;
-    const uint64_t ntiles = (n + kLookupTileRows - 1) / kLookupTileRows, nfull = n / kLookupTileRows;
+    const uint64_t ntiles = rt_ntiles(n), nfull = rt_nfull(n);
     const uint64_t data_bytes1 = (n * c1 + 7) / 8, data_bytes2 = (n * c2 + 7) / 8;
     const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
     uint64_t tile = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
     const uint32_t nts = a.nts, mode = a.mode;
 
-    // tile t of one column: LDS-DMA into `dst` (the last tile: only 16-byte chunks that start inside the payload)
+    // tile t of one column: LDS-DMA into `dst` (the last tile: only 16-byte chunks that start inside the payload).  The kernels' own
+    // copy of rt_issue_tile's loop, as their store dispatch is of store_words_by and `left` of lane_valid_rows (kernels/rt_column.hpp):
+    // with the shared forms 43 of the 64 instantiations take other register counts
     auto issue_column = [&](const uint8_t *packed, uint64_t data_bytes, uint32_t tile_bytes, uint64_t t, uint8_t *dst) {
         const uint64_t first = t * tile_bytes;
         const uint8_t *src = packed + first;
         const uint64_t left = data_bytes - first; // t < ntiles: at least one byte
         const uint32_t lim = left < tile_bytes ? (uint32_t)left : tile_bytes;
 #pragma unroll
-        for (int j = 0; j < 8; j++) { // a tile is at most 8 KiB
+        for (int j = 0; j < kRtDmaInstrs; j++) {
             const uint32_t o = j * 1024 + lane * 16;
             if ((uint32_t)j * 1024u < tile_bytes && o < lim) __builtin_amdgcn_global_load_lds(MI355_GPTR(src + o), MI355_LPTR(dst + j * 1024), 16, 0, AUX);
         }
@@ -153,11 +154,11 @@ template <int CO, bool CHECKED> __device__ __forceinline__ void arith_body(const
     auto store_prev = [&]() {
         uint8_t *dst = out_lane + prev * OUT_TILE;
         if (nts == 2)
-            lookup_store<CO, 2>(dst, res);
+            rt_store<CO, 2>(dst, res);
         else if (nts == 1)
-            lookup_store<CO, 1>(dst, res);
+            rt_store<CO, 1>(dst, res);
         else
-            lookup_store<CO, 0>(dst, res);
+            rt_store<CO, 0>(dst, res);
     };
     while (tile < ntiles) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // both tiles have landed
@@ -165,7 +166,7 @@ template <int CO, bool CHECKED> __device__ __forceinline__ void arith_body(const
         const uint64_t next = tile + stride;
         if (next < ntiles) issue(next, nxt1, nxt2);
 
-        const uint8_t *const base1 = cur1 + (uint32_t)lane * (VPL / 8u * c1), *const base2 = cur2 + (uint32_t)lane * (VPL / 8u * c2);
+        const uint8_t *const base1 = cur1 + (uint32_t)lane * rt_lane_bytes(c1), *const base2 = cur2 + (uint32_t)lane * rt_lane_bytes(c2);
         uint32_t bad = 0;
         // the form of the expression: ONE uniform branch per tile, then 32 rows of straight-line code
 #define MI355_ARITH_MODE(M) case M: arith_rows<CO, CHECKED, M>(a, base1, c1, vmask1, base2, c2, vmask2, res, bad); break
@@ -188,9 +189,9 @@ template <int CO, bool CHECKED> __device__ __forceinline__ void arith_body(const
             prev = tile;
         } else {
             // rows >= n hold stale LDS: they reach neither a stored byte nor the counter
-            const int64_t left = (int64_t)(n - tile * kLookupTileRows) - (int64_t)lane * VPL;
+            const int64_t left = (int64_t)(n - tile * kRtTileRows) - (int64_t)lane * VPL;
             const int valid = left >= VPL ? VPL : (left <= 0 ? 0 : (int)left);
-            lookup_store_tail<CO>(out_lane + tile * OUT_TILE, res, valid);
+            rt_store_tail<CO>(out_lane + tile * OUT_TILE, res, valid);
             bad &= tail_mask(valid, 0);
             prev = ~0ull;
         }
@@ -203,10 +204,7 @@ template <int CO, bool CHECKED> __device__ __forceinline__ void arith_body(const
     if (prev != ~0ull) store_prev();
     if constexpr (CHECKED) {
         if (a.out_of_range) {
-            // 64 lanes x 2^24 stays inside 32 bits: three 24-bit limbs through the 32-bit wave sum
-            const unsigned long long lo = wave_sum((uint32_t)(outside & 0xffffffull)), mid = wave_sum((uint32_t)((outside >> 24) & 0xffffffull)),
-                                     hi = wave_sum((uint32_t)(outside >> 48));
-            const unsigned long long total = lo + (mid << 24) + (hi << 48);
+            const unsigned long long total = wave_sum64(outside);
             if (lane == 0 && total) __hip_atomic_fetch_add(a.out_of_range, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }

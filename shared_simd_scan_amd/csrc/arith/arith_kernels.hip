@@ -19,7 +19,7 @@ namespace {
 // all of a block's LDS is dynamic, sized to the two input widths: the waves' two images of each column
 template <int CO> hipError_t launch_arith(const ArithLaunch &r)
 {
-    const uint64_t ntiles = (r.k.n + kLookupTileRows - 1) / kLookupTileRows;
+    const uint64_t ntiles = rt_ntiles(r.k.n);
     const size_t lds = arith_block_lds(r.k.c1, r.k.c2);
     const int max_dyn = (int)arith_block_lds(32, 32);
 #if MI355_ARITH_CHECKED

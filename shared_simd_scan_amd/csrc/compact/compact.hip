@@ -1,5 +1,5 @@
 // compact.hip -- implementation of include/mi355_compact.h: argument checks, the selection workspace, and the four launches of a
-// call -- rowid_count_kernel and rowid_scan_kernel (kernels/bitmap.hpp, as mi355_bitmap_to_rowids_dev launches them), then
+// call -- rowid_count_kernel and rowid_scan_kernel (kernels/bitmap.hpp, through launch_rowid_prefix of launch_util.hpp), then
 // compact_edges_kernel and compact_kernel<C> (compact/compact.hpp) by width.  Its own translation unit: neither the other entry
 // points nor the width groups rebuild with it.  The last launch is launch_tier (launch_util.hpp) on a LaunchEnv (ctx.hpp), shared
 // with semijoin/ and lookup/.
@@ -55,13 +55,13 @@ int mi355_compact_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
         if (ranges_overlap(out_dev, out_bytes, bitmap_dev, bitmap_bytes(n)))
             return fail(MI355_E_INVALID, "out_dev overlaps bitmap_dev: the bitmap is read while the result is written");
     }
-    // counts and prefix: the passes and the workspace layout of mi355_bitmap_to_rowids_dev
+    // counts and prefix: the chunk prefix over the bitmap (launch_util.hpp rowid_plan)
+    const RowidPlan p = rowid_plan(n);
+    MI355_CHECK(rowid_ws_get(ctx, p.words, "mi355_compact_dev"));
     RowidArgs g{};
     g.bitmap = (const uint8_t *)bitmap_dev;
-    g.nbytes = bitmap_bytes(n);
-    g.nchunks = (g.nbytes + kRowidChunk - 1) / kRowidChunk;
-    const uint64_t ngroups = (g.nchunks + kRowidScanGroup - 1) / kRowidScanGroup;
-    MI355_CHECK(rowid_ws_get(ctx, g.nchunks + 1 + ngroups, "mi355_compact_dev")); // chunk counts, the total, one total per scan group
+    g.nbytes = p.nbytes;
+    g.nchunks = p.nchunks;
     g.chunk_counts = ctx->rowid_ws;
     CompactLaunch r{};
     r.k.packed = (const uint8_t *)packed_dev;
@@ -77,9 +77,7 @@ int mi355_compact_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
     r.env = launch_env(ctx);
     llc_forget(ctx);
     std::string *const rec = r.env.record;
-    const unsigned count_grid = grid_for(g.nchunks, 8, r.env.num_cus);
-    MI355_LAUNCH(rec, 0, rowid_count_kernel, dim3(count_grid), dim3(256), 0, ctx->stream, g);
-    MI355_LAUNCH(rec, 0, rowid_scan_kernel, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, g);
+    launch_rowid_prefix<true>(r.env, p, g);
     // also with capacity == 0: it leaves the total where the copy below takes it from
     MI355_LAUNCH(rec, 0, compact_edges_kernel, dim3((unsigned)((g.nchunks + 255) / 256)), dim3(256), 0, ctx->stream, r.k);
     hipError_t err = hipGetLastError();

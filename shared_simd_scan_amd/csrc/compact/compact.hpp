@@ -3,9 +3,9 @@
 //
 // No block ever waits for another block: where a chunk's values go is known before compact_kernel starts, from the separate
 // launches in front of it (kernels/bitmap.hpp: rowid_count_kernel counts the set bits of every chunk of kRowidChunk bitmap bytes
-// = 16384 rows, rowid_scan_kernel turns the counts into exclusive prefixes inside groups of kRowidScanGroup chunks plus one
-// total per group).  A chunk's first output index is the sum of the totals of the earlier groups plus its prefix, as
-// rowid_write_kernel computes it; its count is the difference to the next prefix (or to its group's total).
+// = 16384 rows, rowid_scan_kernel turns the counts into exclusive prefixes inside scan groups of 1024 chunks plus one
+// total per group).  A chunk's first output index and its count come from that prefix (chunk_span_wave, and chunk_span_serial in
+// compact_edges_kernel: kernels/bitmap.hpp), as rowid_write_kernel's do.
 //
 // Edge dwords.  Chunk k owns the bit range [before_k c, end_k c) of the output, clipped at m c (m = min(total, capacity)).  The
 // whole dwords inside it are its own and get plain stores.  The dword a range starts in (when it does not start on a dword
@@ -17,8 +17,8 @@
 //
 // compact_kernel<C>: persistent grid, a wave per chunk, chunks dealt out by stride.  A chunk whose count is zero (or whose
 // first index is beyond the capacity) is not touched: no bitmap byte, no column byte.  Otherwise the chunk is 8 tiles of 64
-// lanes x 32 consecutive rows (lookup's and group_aggregate's geometry), and lane l's mask of tile t is bitmap dword 64 t + l
-// of the chunk: the lane reads its 8 words up front (words beyond ceil(n/8) bytes bytewise, as rowid_count_kernel does).  A
+// lanes x 32 consecutive rows (the geometry of kernels/rt_column.hpp), and lane l's mask of tile t is bitmap dword 64 t + l
+// of the chunk: the lane reads its 8 words up front (bitmap_word_at: words beyond ceil(n/8) bytes bytewise).  A
 // tile without a set bit (one ballot) moves nothing.  The others travel by LDS-DMA (non-temporal: the column is read once)
 // into one of the wave's two images; the next such tile of the chunk is on its way while the current one is decoded.
 //   decode      the lane's C dwords out of the image into registers, 32 unrolled steps of extract<C, K> under the mask bit:
@@ -40,6 +40,7 @@
 #pragma once
 
 #include "../kernels.hpp"
+#include "../kernels/rt_column.hpp" // the image of a tile; store_words_by
 
 namespace mi355 {
 
@@ -57,45 +58,22 @@ struct CompactArgs {
     uint32_t nts;            // result stores: 0 plain, 1 non-temporal, 2 write-through
 };
 
-constexpr int kCompactTileRows = 64 * 32;                                 // 2048: a lane's mask is one bitmap dword
-constexpr int kCompactTiles = kRowidChunk * 8 / kCompactTileRows;          // 8 tiles per chunk
-// an image of the input tile in whole LDS-DMA instructions; the output stage: 64 C whole dwords, the carry's, the straddle's
-constexpr uint32_t compact_image(uint32_t c) { return (256u * c + 1023u) / 1024u * 1024u; }
+constexpr int kCompactTiles = kRowidChunk * 8 / kRtTileRows;               // 8 tiles per chunk: a lane's mask of a tile is one bitmap dword
+// the output stage: 64 C whole dwords, the carry's, the straddle's; a wave's LDS: two images of the input tile and the stage
 constexpr uint32_t compact_stage_dwords(uint32_t c) { return 64u * c + 4u; }
-constexpr uint32_t compact_wave_lds(uint32_t c) { return 2u * compact_image(c) + 4u * compact_stage_dwords(c); }
+constexpr uint32_t compact_wave_lds(uint32_t c) { return 2u * rt_image(c) + 4u * compact_stage_dwords(c); }
 constexpr uint32_t compact_lds(uint32_t c) { return kWavesPerBlock * compact_wave_lds(c); }
 static_assert(compact_lds(32) <= kCuLdsBytes, "LDS budget");
-
-// where a chunk's values go: `before` values precede it, `count` are its own
-struct CompactSpan {
-    unsigned long long before, count;
-};
-// one thread's view (compact_edges_kernel); `total` gets the grand total
-__device__ __forceinline__ CompactSpan compact_span_serial(const CompactArgs &a, uint64_t ch, unsigned long long &total)
-{
-    const unsigned long long *totals = a.chunk_counts + a.nchunks + 1;
-    const uint64_t ngroups = (a.nchunks + kRowidScanGroup - 1) / kRowidScanGroup, g = ch / kRowidScanGroup;
-    unsigned long long before = 0;
-    total = 0;
-    for (uint64_t i = 0; i < ngroups; i++) {
-        const unsigned long long t = totals[i];
-        total += t;
-        if (i < g) before += t;
-    }
-    const unsigned long long prefix = a.chunk_counts[ch];
-    const bool last_of_group = (ch + 1) % kRowidScanGroup == 0 || ch + 1 == a.nchunks;
-    const unsigned long long next = last_of_group ? totals[g] : a.chunk_counts[ch + 1];
-    return {before + prefix, next - prefix};
-}
 
 // Zeroes the dwords of the output that chunks share, one thread per chunk; thread 0 leaves the total at chunk_counts[nchunks].
 static __global__ __launch_bounds__(256) void compact_edges_kernel(CompactArgs a)
 {
     const uint64_t ch = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= a.nchunks) return;
+    const ChunkPrefix prefix{a.chunk_counts, a.nchunks};
     unsigned long long total;
-    const CompactSpan s = compact_span_serial(a, ch, total);
-    if (ch == 0) a.chunk_counts[a.nchunks] = total;
+    const ChunkSpan s = chunk_span_serial(prefix, ch, total);
+    if (ch == 0) *prefix.total() = total;
     if (s.count == 0 || s.before >= a.capacity) return;
     const unsigned long long m = total < a.capacity ? total : a.capacity;
     const unsigned long long end = s.before + s.count < a.capacity ? s.before + s.count : a.capacity;
@@ -111,12 +89,6 @@ static __global__ __launch_bounds__(256) void compact_edges_kernel(CompactArgs a
     const unsigned long long B = s.before * a.c, E = end * a.c;
     if (B & 31) zero(B >> 5);
     if (E & 31) zero(E >> 5);
-}
-
-__device__ __forceinline__ unsigned long long compact_uniform(unsigned long long v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 // one of the lane's mask words by a wave-uniform index, without indexing the register array
@@ -146,27 +118,21 @@ __device__ __forceinline__ void compact_decode(const uint32_t (&w)[C], uint32_t 
         if (pos < room) compact_put<C>(stage, carry, pos, extract<C, K, C>(w));
         pos++;
     }
-    if constexpr (K + 1 < 32) compact_decode<C, K + 1>(w, mask, stage, carry, pos, room);
-}
-
-template <int NT> __device__ __forceinline__ void compact_store(uint32_t *dst, uint32_t v)
-{
-    const uint32_t one[1] = {v};
-    store_words<1, NT>((uint8_t *)dst, one);
+    if constexpr (K + 1 < kRtVpl) compact_decode<C, K + 1>(w, mask, stage, carry, pos, room);
 }
 
 template <int C> __global__ __launch_bounds__(kBlockThreads) void compact_kernel(CompactArgs a)
 {
     constexpr int AUX = 2; // the column is streamed once: non-temporal DMA
-    constexpr uint32_t TILE_BYTES = 256u * C;
+    constexpr uint32_t TILE_BYTES = rt_tile_bytes(C);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t *const images = mi355_dyn_lds + (uint32_t)wave * compact_wave_lds(C);
-    uint32_t *const stage = (uint32_t *)(images + 2u * compact_image(C));
+    uint32_t *const stage = (uint32_t *)(images + 2u * rt_image(C));
     for (uint32_t j = lane; j < compact_stage_dwords(C); j += 64) stage[j] = 0;
 
     const uint64_t data_bytes = (a.n * C + 7) / 8;
-    const unsigned long long *const totals = a.chunk_counts + a.nchunks + 1;
+    const ChunkPrefix prefix{a.chunk_counts, a.nchunks};
     const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
     const uint32_t nts = a.nts;
 
@@ -180,16 +146,8 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void compact_kernel
     };
 
     for (uint64_t ch = (uint64_t)blockIdx.x * kWavesPerBlock + wave; ch < a.nchunks; ch += stride) {
-        // values before this chunk = totals of the earlier scan groups + the chunk's prefix inside its group
-        const uint64_t g = ch / kRowidScanGroup;
-        unsigned long long before = 0;
-        for (uint64_t i = lane; i < g; i += 64) before += totals[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-        const unsigned long long prefix = a.chunk_counts[ch];
-        const bool last_of_group = (ch + 1) % kRowidScanGroup == 0 || ch + 1 == a.nchunks;
-        const unsigned long long count = compact_uniform((last_of_group ? totals[g] : a.chunk_counts[ch + 1]) - prefix);
-        before = compact_uniform(before + prefix);
+        const ChunkSpan span = chunk_span_wave(prefix, ch, lane); // the values in front of this chunk, and its own
+        const unsigned long long before = span.before, count = span.count;
         if (count == 0 || before >= a.capacity) continue; // nothing of this chunk is read
         const uint32_t room = (uint32_t)(a.capacity - before < count ? a.capacity - before : count); // <= 16384
 
@@ -198,13 +156,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void compact_kernel
         uint32_t live = 0;
 #pragma unroll
         for (int t = 0; t < kCompactTiles; t++) {
-            const uint64_t o = ch * kRowidChunk + (uint64_t)(t * 64 + lane) * 4;
-            uint32_t w = 0;
-            if (o + 4 <= a.nbytes)
-                w = *(const uint32_t *)(a.bitmap + o);
-            else
-                for (int b = 0; b < 4; b++)
-                    if (o + b < a.nbytes) w |= (uint32_t)a.bitmap[o + b] << (8 * b);
+            const uint32_t w = bitmap_word_at(a.bitmap, a.nbytes, ch * kRowidChunk + (uint64_t)(t * 64 + lane) * 4);
             m[t] = w;
             if (__ballot(w != 0)) live |= 1u << t;
         }
@@ -222,11 +174,11 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void compact_kernel
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the tile has landed
             live &= live - 1;
             const int next = live ? __builtin_ctz(live) : -1;
-            if (next >= 0) issue(ch * kCompactTiles + next, images + (uint32_t)(buf ^ 1) * compact_image(C));
+            if (next >= 0) issue(ch * kCompactTiles + next, images + (uint32_t)(buf ^ 1) * rt_image(C));
 
             const uint32_t mask = compact_pick(m, cur);
             uint32_t w[C];
-            read_lane_data<C, 32>(images + (uint32_t)buf * compact_image(C), lane, w);
+            read_lane_data<C, kRtVpl>(images + (uint32_t)buf * rt_image(C), lane, w);
             const uint32_t mine = __builtin_popcount(mask);
             const uint32_t incl = wave_inclusive_scan(mine);
             uint32_t in_tile = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -242,14 +194,11 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void compact_kernel
             for (uint32_t j = lane; j < whole; j += 64) {
                 const uint32_t v = stage[j];
                 stage[j] = 0;
+                const uint32_t one[1] = {v};
                 if (shared_first && j == 0)
                     atomicOr(dst, v);
-                else if (nts == 2)
-                    compact_store<2>(dst + j, v);
-                else if (nts == 1)
-                    compact_store<1>(dst + j, v);
                 else
-                    compact_store<0>(dst + j, v);
+                    store_words_by<1>((uint8_t *)(dst + j), one, nts);
             }
             if (whole) {
                 // the bits behind the last whole dword move to the front of the stage

@@ -175,22 +175,19 @@ int mi355_bitmap_to_rowids_dev(mi355_ctx *ctx, const void *bitmap_dev, uint64_t 
     }
     MI355_CHECK(check_dev(bitmap_dev, 4, "bitmap_dev"));
     if (capacity) MI355_CHECK(check_ptr(rowids_dev, "rowids_dev"));
+    const RowidPlan p = rowid_plan(n);
+    MI355_CHECK(rowid_ws_get(ctx, p.words, "mi355_bitmap_to_rowids_dev"));
     RowidArgs g;
     g.bitmap = (const uint8_t *)bitmap_dev;
-    g.nbytes = bitmap_bytes(n);
+    g.nbytes = p.nbytes;
     g.first_row = first_row;
-    g.nchunks = (g.nbytes + kRowidChunk - 1) / kRowidChunk;
-    const uint64_t ngroups = (g.nchunks + kRowidScanGroup - 1) / kRowidScanGroup;
-    const uint64_t ws_entries = g.nchunks + 1 + ngroups; // chunk counts, the total, one total per scan group
-    MI355_CHECK(rowid_ws_get(ctx, ws_entries, "mi355_bitmap_to_rowids_dev"));
+    g.nchunks = p.nchunks;
     g.chunk_counts = ctx->rowid_ws;
     g.rowids = rowids_dev;
     g.capacity = capacity;
-    const unsigned grid = capped_grid(ctx, (g.nchunks + 3) / 4, 8, false);
-    std::string *const rec = &ctx->last_launch;
-    MI355_LAUNCH(rec, 0, rowid_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
-    MI355_LAUNCH(rec, 0, rowid_scan_kernel, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, g);
-    MI355_LAUNCH(rec, 0, rowid_write_kernel, dim3(grid), dim3(256), 0, ctx->stream, g);
+    const LaunchEnv env = launch_env(ctx);
+    launch_rowid_prefix<true>(env, p, g);
+    MI355_LAUNCH(env.record, 0, rowid_write_kernel, dim3(rowid_chunk_grid(p, env.num_cus)), dim3(256), 0, ctx->stream, g);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(count_dev, g.chunk_counts + g.nchunks, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
     return MI355_OK;

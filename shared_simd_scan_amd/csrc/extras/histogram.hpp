@@ -6,6 +6,7 @@
 
 #include "../dispatch.hpp"
 #include "../kernels.hpp"
+#include "../kernels/rt_column.hpp" // lane_valid_rows: the ragged last tile
 
 namespace mi355 {
 
@@ -77,8 +78,7 @@ __global__ __launch_bounds__(kBlockThreads) void histogram_kernel(HistArgs a)
         }
         const bool full = tile < tc.nfull;
         if (!full) { // rows behind the column count for nothing
-            const int64_t left = (int64_t)(a.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL;
-            const int valid = left >= VPL ? VPL : (left <= 0 ? 0 : (int)left);
+            const int valid = lane_valid_rows<VPL>(a.n, tile, lane);
 #pragma unroll
             for (int j = 0; j < WORDS; j++) m[j] &= tail_mask(valid, j);
         }

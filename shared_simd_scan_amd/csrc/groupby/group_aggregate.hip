@@ -31,7 +31,7 @@ void launch_init(const LaunchEnv &env, unsigned long long *out, unsigned ck)
 
 template <int CK> hipError_t launch_group(const GroupLaunch &r)
 {
-    using G = ScanGeom<CK, kGroupVpl>;
+    using G = ScanGeom<CK, kRtVpl>;
     const uint32_t cv = r.k.cv;
     const uint64_t ntiles = (r.k.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
     const size_t lds = group_block_lds<CK>(cv);

@@ -5,7 +5,8 @@
 // Pipeline.  scan_columns_kernel's run-time-width form (predicates/columns.hpp, SAME = false): a wave owns tiles of
 // 64 x 32 consecutive rows, lane l rows [32 l, 32 l + 32) of BOTH columns.  The kernel is a template of the KEY width only
 // (12 instantiations): the keys' tile travels by LDS-DMA into one image per wave, is read into registers and decoded at
-// compile-time bit offsets (extract<CK, K>).  The value width cv is a wave-uniform run-time number: the values' tile stays
+// compile-time bit offsets (extract<CK, K>).  The value width cv is a wave-uniform run-time number: the values' tile is the
+// run-time-width stream of kernels/rt_column.hpp (its geometry and decode; the DMA loop is the kernel's own copy), stays
 // in LDS and is decoded from there (columns_lds_value), so a wave has two images of it and alternates -- the next tile
 // lands in one while the other is decoded.  The mask word of a lane's 32 rows is loaded one tile ahead like
 // aggregate_kernel's (extras/aggregate.hpp); the ragged tile reads only the ceil(n / 8) bytes a bitmap is guaranteed to
@@ -30,12 +31,11 @@
 #pragma once
 
 #include "../kernels.hpp"
-#include "../predicates/columns.hpp" // columns_lds_value: a value of run-time width out of LDS
+#include "../kernels/rt_column.hpp" // the values: the tile stream of a column of run-time width
 
 namespace mi355 {
 
 constexpr int kGroupMaxBits = 12;                 // MI355_GROUP_MAX_KEY_BITS: 2^12 x 20 B = 80 KiB next to the tiles
-constexpr int kGroupVpl = 32;                     // rows per lane and tile: the run-time-width decode's geometry
 constexpr uint32_t kGroupEntryBytes = 20;         // sum 8, count 4, min 4, max 4
 constexpr uint32_t kGroupTableBudget = 10 * 1024; // bytes of LDS the replicated table may take (one copy may take more)
 
@@ -56,9 +56,8 @@ constexpr uint32_t group_copies(int ck)
     return r;
 }
 constexpr uint32_t group_table_bytes(int ck) { return (kGroupEntryBytes << ck) * group_copies(ck); } // a multiple of 16
-// an image of the values' tile: 64 lanes x 32 rows x cv bits, in whole LDS-DMA instructions
-constexpr uint32_t group_value_image(uint32_t cv) { return (64u * kGroupVpl * cv / 8 + 1023u) / 1024u * 1024u; }
-template <int CK> constexpr uint32_t group_wave_lds(uint32_t cv) { return (uint32_t)ScanGeom<CK, kGroupVpl>::LDS_BYTES + 2u * group_value_image(cv); }
+// a wave's images: the keys' tile and two of the values'
+template <int CK> constexpr uint32_t group_wave_lds(uint32_t cv) { return (uint32_t)ScanGeom<CK, kRtVpl>::LDS_BYTES + 2u * rt_image(cv); }
 // + 16: the dword behind the last lane's run of values is read (and not used), as in scan_columns_kernel
 template <int CK> constexpr uint32_t group_block_lds(uint32_t cv) { return group_table_bytes(CK) + kWavesPerBlock * group_wave_lds<CK>(cv) + 16u; }
 
@@ -74,17 +73,17 @@ static __global__ void group_aggregate_init_kernel(unsigned long long *out, uint
 
 // the lane's 32 keys (registers, compile-time offsets) and values (LDS, scalar offsets)
 template <int CK, int K> __device__ __forceinline__ void group_decode(const uint32_t (&w)[CK], const uint8_t *base, uint32_t cv, uint32_t vmask,
-                                                                      uint32_t (&key)[kGroupVpl], uint32_t (&x)[kGroupVpl])
+                                                                      uint32_t (&key)[kRtVpl], uint32_t (&x)[kRtVpl])
 {
     key[K] = extract<CK, K, CK>(w);
     x[K] = columns_lds_value<K>(base, cv, vmask);
-    if constexpr (K + 1 < kGroupVpl) group_decode<CK, K + 1>(w, base, cv, vmask, key, x);
+    if constexpr (K + 1 < kRtVpl) group_decode<CK, K + 1>(w, base, cv, vmask, key, x);
 }
 
 template <int CK> __global__ __launch_bounds__(kBlockThreads, 2) void group_aggregate_kernel(GroupArgs a)
 {
     static_assert(CK >= 1 && CK <= kGroupMaxBits, "the groups' state must fit in LDS");
-    constexpr int VPL = kGroupVpl;
+    constexpr int VPL = kRtVpl;
     using G = ScanGeom<CK, VPL>;
     static_assert(G::WORDS == 1 && G::LANE_DWORDS == CK, "32 rows per lane: one mask word, CK key dwords");
     constexpr int AUX = 2; // both columns are streamed once: non-temporal DMA
@@ -103,12 +102,12 @@ template <int CK> __global__ __launch_bounds__(kBlockThreads, 2) void group_aggr
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t cv = a.cv;
-    const uint32_t tile_bytes2 = 64u * VPL / 8u * cv; // a multiple of 256
-    const uint32_t lds2_bytes = group_value_image(cv);
-    uint8_t *const lds1 = mi355_dyn_lds + group_table_bytes(CK) + (uint32_t)wave * ((uint32_t)G::LDS_BYTES + 2u * lds2_bytes);
+    const uint32_t tile_bytes2 = rt_tile_bytes(cv); // a multiple of 256
+    const uint32_t image2 = rt_image(cv);
+    uint8_t *const lds1 = mi355_dyn_lds + group_table_bytes(CK) + (uint32_t)wave * ((uint32_t)G::LDS_BYTES + 2u * image2);
     uint8_t *lds2 = lds1 + G::LDS_BYTES;   // the values' image being decoded ...
-    uint8_t *lds2_next = lds2 + lds2_bytes; // ... and where their next tile lands
-    const uint32_t vmask = cv >= 32 ? 0xffffffffu : ((1u << cv) - 1u);
+    uint8_t *lds2_next = lds2 + image2;     // ... and where their next tile lands
+    const uint32_t vmask = rt_vmask(cv);
     const uint32_t copy = (uint32_t)lane & (R - 1u);
 
     const TileCtx<CK, VPL> tc(a.n);
@@ -120,12 +119,13 @@ template <int CK> __global__ __launch_bounds__(kBlockThreads, 2) void group_aggr
     // tile t of both columns: LDS-DMA into the wave's images (the values': into `dst2`)
     auto issue = [&](uint64_t t, uint8_t *dst2) {
         tc.template issue<AUX>(a.keys, t, lds1, lane);
+        // (the kernel's own copy of rt_issue_tile's loop: behind tc.issue in one lambda the shared form compiles to another schedule)
         const uint64_t first = t * tile_bytes2;
         const uint8_t *src = a.values + first;
         const uint64_t left = data_bytes2 - first; // t < ntiles: at least one byte
         const uint32_t lim = left < tile_bytes2 ? (uint32_t)left : tile_bytes2;
 #pragma unroll
-        for (int j = 0; j < 8; j++) { // a tile of values is at most 8 KiB
+        for (int j = 0; j < kRtDmaInstrs; j++) {
             const uint32_t o = j * 1024 + lane * 16;
             if ((uint32_t)j * 1024u < tile_bytes2 && o < lim) __builtin_amdgcn_global_load_lds(MI355_GPTR(src + o), MI355_LPTR(dst2 + j * 1024), 16, 0, AUX);
         }
@@ -168,12 +168,12 @@ template <int CK> __global__ __launch_bounds__(kBlockThreads, 2) void group_aggr
         }
         const bool full = tile < tc.nfull;
         if (!full) { // rows behind the column count for nothing
-            const int64_t left = (int64_t)(a.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL;
+            const int64_t left = (int64_t)(a.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL; // (lane_valid_rows compiles to another schedule)
             const int valid = left >= VPL ? VPL : (left <= 0 ? 0 : (int)left);
             m &= tail_mask(valid, 0);
         }
         uint32_t key[VPL], x[VPL];
-        group_decode<CK, 0>(w, lds2 + (uint32_t)lane * (VPL / 8u * cv), cv, vmask, key, x);
+        group_decode<CK, 0>(w, lds2 + (uint32_t)lane * rt_lane_bytes(cv), cv, vmask, key, x);
         const bool all = !a.mask && full; // wave-uniform
 #pragma unroll
         for (int v0 = 0; v0 < VPL; v0 += 8) {

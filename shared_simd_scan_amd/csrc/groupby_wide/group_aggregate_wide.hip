@@ -77,7 +77,7 @@ int mi355_group_aggregate_wide_dev(mi355_ctx *ctx, const void *keys_dev, unsigne
     llc_forget(ctx);
     launch_init(env, k);
     if (n) {
-        const uint64_t ntiles = (n + kLookupTileRows - 1) / kLookupTileRows;
+        const uint64_t ntiles = rt_ntiles(n);
         const size_t lds = group_wide_block_lds(k.slots, ck, cv);
         allow_dynamic_lds<group_aggregate_wide_kernel>((int)group_wide_max_lds(), env.device);
         // Blocks per CU: what registers and this launch's LDS admit, at most four (table_bpc: the occupancy query is asked once

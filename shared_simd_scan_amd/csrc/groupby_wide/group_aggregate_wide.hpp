@@ -3,9 +3,9 @@
 // (group_aggregate_kernel, groupby/group_aggregate.hpp, keeps it in LDS and stops at 2^12).  gfx950 only; part of
 // libmi355scan.so through groupby_wide/group_aggregate_wide.hip.
 //
-// Pipeline.  arith_body's input half (arith/arith.hpp): a wave owns tiles of 64 x 32 consecutive rows, lane l rows
-// [32 l, 32 l + 32) of BOTH columns.  ONE kernel, no template of a width: both widths are wave-uniform run-time numbers, both
-// tiles travel by non-temporal LDS-DMA, stay in LDS and are decoded from there (columns_lds_value), so a wave has two
+// Pipeline.  The run-time-width tile stream of kernels/rt_column.hpp, twice: a wave owns tiles of 64 x 32 consecutive rows, lane l
+// rows [32 l, 32 l + 32) of BOTH columns.  ONE kernel, no template of a width: both widths are wave-uniform run-time numbers, both
+// tiles travel by non-temporal LDS-DMA (rt_issue_tile), stay in LDS and are decoded from there (columns_lds_value), so a wave has two
 // alternating images of EACH column -- the next tiles land in one pair while the other is decoded.  The mask word of a lane's
 // 32 rows is loaded one tile ahead and the ragged tile handled as in group_aggregate_kernel: only the ceil(n / 8) bytes a
 // bitmap is guaranteed to hold are read, rows >= n are masked off, so what lies behind the columns never reaches a result.
@@ -33,8 +33,7 @@
 #pragma once
 
 #include "../kernels.hpp"
-#include "../lookup/lookup.hpp"      // lookup_image, kLookupVpl, kLookupTileRows: the geometry of a run-time-width tile
-#include "../predicates/columns.hpp" // columns_lds_value: a value of run-time width out of LDS
+#include "../kernels/rt_column.hpp" // the tile stream of a column of run-time width: geometry, DMA, decode
 
 namespace mi355 {
 
@@ -60,7 +59,7 @@ struct GroupWideArgs {
 };
 
 // a wave's images: two of each column
-constexpr uint32_t group_wide_wave_lds(uint32_t ck, uint32_t cv) { return 2u * lookup_image(ck) + 2u * lookup_image(cv); }
+constexpr uint32_t group_wide_wave_lds(uint32_t ck, uint32_t cv) { return 2u * rt_image(ck) + 2u * rt_image(cv); }
 // + 16: the dword behind the last lane's run is read (and not used)
 constexpr uint32_t group_wide_block_lds(uint32_t slots, uint32_t ck, uint32_t cv)
 {
@@ -188,9 +187,9 @@ __device__ __forceinline__ uint32_t group_wide_rows(const GroupWideFront &f, uns
 
 static __global__ __launch_bounds__(kBlockThreads) void group_aggregate_wide_kernel(GroupWideArgs a)
 {
-    constexpr int VPL = kLookupVpl;
+    constexpr int VPL = kRtVpl;
     constexpr int AUX = 2; // both columns are streamed once: non-temporal DMA
-    constexpr uint32_t MASK_TILE = kLookupTileRows / 8; // mask bytes of a tile
+    constexpr uint32_t MASK_TILE = kRtTileRows / 8; // mask bytes of a tile
     const uint32_t slots = a.slots;
     const GroupWideFront f(mi355_dyn_lds, slots);
     for (uint32_t k = threadIdx.x; k < slots; k += kBlockThreads) {
@@ -204,36 +203,24 @@ static __global__ __launch_bounds__(kBlockThreads) void group_aggregate_wide_ker
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t ck = a.ck, cv = a.cv, groups = a.groups;
-    const uint32_t tile_bytes1 = 64u * VPL / 8u * ck, tile_bytes2 = 64u * VPL / 8u * cv; // multiples of 256
-    const uint32_t image1 = lookup_image(ck), image2 = lookup_image(cv);
+    const uint32_t tile_bytes1 = rt_tile_bytes(ck), tile_bytes2 = rt_tile_bytes(cv); // multiples of 256
+    const uint32_t image1 = rt_image(ck), image2 = rt_image(cv);
     uint8_t *cur1 = mi355_dyn_lds + kGroupWideSlotBytes * slots + (uint32_t)wave * group_wide_wave_lds(ck, cv); // the images being decoded ...
     uint8_t *nxt1 = cur1 + image1;                                                                              // ... and where the next tiles land
     uint8_t *cur2 = cur1 + 2u * image1;
     uint8_t *nxt2 = cur2 + image2;
-    const uint32_t kmask = ck >= 32 ? 0xffffffffu : ((1u << ck) - 1u), vmask = cv >= 32 ? 0xffffffffu : ((1u << cv) - 1u);
+    const uint32_t kmask = rt_vmask(ck), vmask = rt_vmask(cv);
 
     const uint64_t n = a.n;
-    const uint64_t ntiles = (n + kLookupTileRows - 1) / kLookupTileRows, nfull = n / kLookupTileRows;
+    const uint64_t ntiles = rt_ntiles(n), nfull = rt_nfull(n);
     const uint64_t data_bytes1 = (n * ck + 7) / 8, data_bytes2 = (n * cv + 7) / 8;
     const uint64_t mask_bytes = (n + 7) / 8;
     const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
     uint64_t tile = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
 
-    // tile t of one column: LDS-DMA into `dst` (the last tile: only 16-byte chunks that start inside the payload)
-    auto issue_column = [&](const uint8_t *packed, uint64_t data_bytes, uint32_t tile_bytes, uint64_t t, uint8_t *dst) {
-        const uint64_t first = t * tile_bytes;
-        const uint8_t *src = packed + first;
-        const uint64_t left = data_bytes - first; // t < ntiles: at least one byte
-        const uint32_t lim = left < tile_bytes ? (uint32_t)left : tile_bytes;
-#pragma unroll
-        for (int j = 0; j < 8; j++) { // a tile is at most 8 KiB
-            const uint32_t o = j * 1024 + lane * 16;
-            if ((uint32_t)j * 1024u < tile_bytes && o < lim) __builtin_amdgcn_global_load_lds(MI355_GPTR(src + o), MI355_LPTR(dst + j * 1024), 16, 0, AUX);
-        }
-    };
     auto issue = [&](uint64_t t, uint8_t *dst1, uint8_t *dst2) {
-        issue_column(a.keys, data_bytes1, tile_bytes1, t, dst1);
-        issue_column(a.values, data_bytes2, tile_bytes2, t, dst2);
+        rt_issue_tile<AUX>(a.keys, data_bytes1, tile_bytes1, t, dst1, lane);
+        rt_issue_tile<AUX>(a.values, data_bytes2, tile_bytes2, t, dst2, lane);
     };
     // the lane's mask word of tile t (ragged end: only the bytes the bitmap is guaranteed to hold)
     auto load_mask = [&](uint64_t t) -> uint32_t {
@@ -263,11 +250,11 @@ static __global__ __launch_bounds__(kBlockThreads) void group_aggregate_wide_ker
             mnext = load_mask(next);
         }
         if (tile >= nfull) { // rows behind the column count for nothing
-            const int64_t left = (int64_t)(n - tile * kLookupTileRows) - (int64_t)lane * VPL;
+            const int64_t left = (int64_t)(n - tile * kRtTileRows) - (int64_t)lane * VPL; // (lane_valid_rows compiles to another schedule)
             const int valid = left >= VPL ? VPL : (left <= 0 ? 0 : (int)left);
             m &= tail_mask(valid, 0);
         }
-        const uint8_t *const kbase = cur1 + (uint32_t)lane * (VPL / 8u * ck), *const vbase = cur2 + (uint32_t)lane * (VPL / 8u * cv);
+        const uint8_t *const kbase = cur1 + (uint32_t)lane * rt_lane_bytes(ck), *const vbase = cur2 + (uint32_t)lane * rt_lane_bytes(cv);
         uint32_t bad = group_wide_rows<0>(f, a.out, groups, kbase, ck, kmask, vbase, cv, vmask, m & 0xffu);
         bad |= group_wide_rows<8>(f, a.out, groups, kbase, ck, kmask, vbase, cv, vmask, (m >> 8) & 0xffu) << 8;
         bad |= group_wide_rows<16>(f, a.out, groups, kbase, ck, kmask, vbase, cv, vmask, (m >> 16) & 0xffu) << 16;
@@ -290,10 +277,7 @@ static __global__ __launch_bounds__(kBlockThreads) void group_aggregate_wide_ker
         }
     }
     if (a.dropped) {
-        // 64 lanes x 2^24 stays inside 32 bits: three 24-bit limbs through the 32-bit wave sum
-        const unsigned long long l0 = wave_sum((uint32_t)(dropped & 0xffffffull)), l1 = wave_sum((uint32_t)((dropped >> 24) & 0xffffffull)),
-                                 l2 = wave_sum((uint32_t)(dropped >> 48));
-        const unsigned long long total = l0 + (l1 << 24) + (l2 << 48);
+        const unsigned long long total = wave_sum64(dropped);
         if (lane == 0 && total) __hip_atomic_fetch_add(a.dropped, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }

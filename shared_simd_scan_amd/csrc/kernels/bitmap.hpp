@@ -1,4 +1,5 @@
-// kernels/bitmap.hpp -- bitmap consumers: combine / count / row ids.  Part of kernels.hpp (gfx950 only).
+// kernels/bitmap.hpp -- bitmap consumers: combine / count / row ids, and the chunk prefix over a bitmap that the row ids, compact/
+// and topk/ share (ChunkPrefix, chunk_span_wave / chunk_span_serial, bitmap_word_at).  Part of kernels.hpp (gfx950 only).
 #pragma once
 
 #include "tile.hpp"
@@ -68,6 +69,17 @@ static __global__ __launch_bounds__(64) void sum_slots_kernel(unsigned long long
 // the chunk counts, in groups.  Pass 3 (rowid_write_kernel): each wave expands its chunk.
 constexpr int kRowidChunk = 2048; // bytes of bitmap per wave = 16384 rows
 
+// the bitmap's dword at byte `o`, safe at the ragged end: the whole dword if it lies inside the nbytes = ceil(n / 8) a bitmap is
+// guaranteed to hold, else the bytes below nbytes
+__device__ __forceinline__ uint32_t bitmap_word_at(const uint8_t *bitmap, uint64_t nbytes, uint64_t o)
+{
+    if (o + 4 <= nbytes) return *(const uint32_t *)(bitmap + o);
+    uint32_t w = 0;
+    for (int b = 0; b < 4; b++)
+        if (o + b < nbytes) w |= (uint32_t)bitmap[o + b] << (8 * b);
+    return w;
+}
+
 struct RowidArgs {
     const uint8_t *bitmap;
     uint64_t nbytes;
@@ -88,16 +100,8 @@ static __global__ __launch_bounds__(256) void rowid_count_kernel(RowidArgs g)
         const uint64_t base = ch * kRowidChunk;
         uint32_t cnt = 0;
 #pragma unroll
-        for (int k = 0; k < kRowidChunk / (64 * 4); k++) {
-            const uint64_t o = base + (uint64_t)(k * 64 + lane) * 4;
-            uint32_t w = 0;
-            if (o + 4 <= g.nbytes)
-                w = *(const uint32_t *)(g.bitmap + o);
-            else
-                for (int b = 0; b < 4; b++)
-                    if (o + b < g.nbytes) w |= (uint32_t)g.bitmap[o + b] << (8 * b);
-            cnt += __builtin_popcount(w);
-        }
+        for (int k = 0; k < kRowidChunk / (64 * 4); k++)
+            cnt += __builtin_popcount(bitmap_word_at(g.bitmap, g.nbytes, base + (uint64_t)(k * 64 + lane) * 4));
         cnt = wave_sum(cnt);
         if (lane == 0) g.chunk_counts[ch] = cnt;
     }
@@ -110,7 +114,66 @@ static __global__ __launch_bounds__(256) void rowid_count_kernel(RowidArgs g)
 // at low selectivity.
 constexpr int kRowidScanGroup = 1024;
 
-__device__ __forceinline__ unsigned long long *rowid_group_totals(const RowidArgs &g) { return g.chunk_counts + g.nchunks + 1; }
+// The prefix part of the selection workspace as pass 2 leaves it: nchunks prefixes (exclusive inside each scan group), the slot
+// of the grand total, one total per scan group.  rowid_prefix_words() is its size; the kernels that consume it (pass 3 below,
+// compact/, topk/) ask chunk_span_wave / chunk_span_serial where a chunk's items go.
+constexpr uint64_t rowid_scan_groups(uint64_t nchunks) { return (nchunks + kRowidScanGroup - 1) / kRowidScanGroup; }
+constexpr uint64_t rowid_prefix_words(uint64_t nchunks) { return nchunks + 1 + rowid_scan_groups(nchunks); }
+struct ChunkPrefix {
+    unsigned long long *counts;
+    uint64_t nchunks;
+    __device__ __forceinline__ unsigned long long *total() const { return counts + nchunks; }
+    __device__ __forceinline__ unsigned long long *group_totals() const { return counts + nchunks + 1; }
+    __device__ __forceinline__ uint64_t ngroups() const { return rowid_scan_groups(nchunks); }
+};
+// where a chunk's items go: `before` of them precede it, `count` are its own
+struct ChunkSpan {
+    unsigned long long before, count;
+};
+
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+// the sum of the first `groups` group totals, by the 64 lanes of a wave (the same in every lane)
+__device__ __forceinline__ unsigned long long chunk_groups_sum(const ChunkPrefix &p, uint64_t groups, int lane)
+{
+    const unsigned long long *const totals = p.group_totals();
+    unsigned long long s = 0;
+    for (uint64_t i = lane; i < groups; i += 64) s += totals[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+// A wave's view of chunk ch, wave-uniform: before = the totals of the earlier scan groups + the chunk's prefix inside its group;
+// count = the next prefix, or its group's total, minus its own prefix.
+__device__ __forceinline__ ChunkSpan chunk_span_wave(const ChunkPrefix &p, uint64_t ch, int lane)
+{
+    const uint64_t g = ch / kRowidScanGroup;
+    const unsigned long long before = chunk_groups_sum(p, g, lane);
+    const unsigned long long prefix = p.counts[ch];
+    const bool last_of_group = (ch + 1) % kRowidScanGroup == 0 || ch + 1 == p.nchunks;
+    const unsigned long long count = uniform64((last_of_group ? p.group_totals()[g] : p.counts[ch + 1]) - prefix);
+    return {uniform64(before + prefix), count};
+}
+// One thread's view of chunk ch (a kernel with a thread per chunk); `total` gets the grand total.
+__device__ __forceinline__ ChunkSpan chunk_span_serial(const ChunkPrefix &p, uint64_t ch, unsigned long long &total)
+{
+    const unsigned long long *const totals = p.group_totals();
+    const uint64_t ngroups = p.ngroups(), g = ch / kRowidScanGroup;
+    unsigned long long before = 0;
+    total = 0;
+    for (uint64_t i = 0; i < ngroups; i++) {
+        const unsigned long long t = totals[i];
+        total += t;
+        if (i < g) before += t;
+    }
+    const unsigned long long prefix = p.counts[ch];
+    const bool last_of_group = (ch + 1) % kRowidScanGroup == 0 || ch + 1 == p.nchunks;
+    const unsigned long long next = last_of_group ? totals[g] : p.counts[ch + 1];
+    return {before + prefix, next - prefix};
+}
 
 static __global__ __launch_bounds__(256) void rowid_scan_kernel(RowidArgs g)
 {
@@ -136,7 +199,7 @@ static __global__ __launch_bounds__(256) void rowid_scan_kernel(RowidArgs g)
         if (i0 + j < g.nchunks) g.chunk_counts[i0 + j] = run;
         run += v[j];
     }
-    if (threadIdx.x == 255) rowid_group_totals(g)[blockIdx.x] = run;
+    if (threadIdx.x == 255) ChunkPrefix{g.chunk_counts, g.nchunks}.group_totals()[blockIdx.x] = run;
 }
 
 // Pass 3.  A step covers 64 lanes x 32 bits = 2048 rows.  Each lane expands its word into a wave-private LDS buffer
@@ -150,32 +213,17 @@ static __global__ __launch_bounds__(256) void rowid_write_kernel(RowidArgs g)
     uint16_t *const st = stage[threadIdx.x >> 6];
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    const unsigned long long *totals = rowid_group_totals(g);
+    const ChunkPrefix prefix{g.chunk_counts, g.nchunks};
     if (wave == 0) { // the grand total, for the caller's count
-        const uint64_t ngroups = (g.nchunks + kRowidScanGroup - 1) / kRowidScanGroup;
-        unsigned long long s = 0;
-        for (uint64_t i = lane; i < ngroups; i += 64) s += totals[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (lane == 0) g.chunk_counts[g.nchunks] = s;
+        const unsigned long long s = chunk_groups_sum(prefix, prefix.ngroups(), lane);
+        if (lane == 0) *prefix.total() = s;
     }
     for (uint64_t ch = wave; ch < g.nchunks; ch += nwaves) {
         const uint64_t base = ch * kRowidChunk;
-        // ids before this chunk = totals of the earlier scan groups + the chunk's prefix inside its group
-        unsigned long long before = 0;
-        for (uint64_t i = lane; i < ch / kRowidScanGroup; i += 64) before += totals[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-        uint64_t out = before + g.chunk_counts[ch];
+        uint64_t out = chunk_span_wave(prefix, ch, lane).before; // ids before this chunk
 #pragma unroll 1
         for (int k = 0; k < kRowidChunk / (64 * 4); k++) {
-            const uint64_t o = base + (uint64_t)(k * 64 + lane) * 4;
-            uint32_t w = 0;
-            if (o + 4 <= g.nbytes)
-                w = *(const uint32_t *)(g.bitmap + o);
-            else
-                for (int b = 0; b < 4; b++)
-                    if (o + b < g.nbytes) w |= (uint32_t)g.bitmap[o + b] << (8 * b);
+            uint32_t w = bitmap_word_at(g.bitmap, g.nbytes, base + (uint64_t)(k * 64 + lane) * 4);
             // exclusive prefix of the lanes' popcounts inside the wave
             const uint32_t c = __builtin_popcount(w);
             uint32_t incl = c;

@@ -1,6 +1,7 @@
 // launch_util.hpp -- the host-side launch helpers that the translation units with a launcher share, one copy of each: capi.hip,
 // extras.hip, the three group units (width_group.hip, predicates/where_group.hip, predicates/columns_group.hip) and the feature
-// units (groupby/group_aggregate.hip, groupby_wide/group_aggregate_wide.hip, semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith_kernels.hip).  No device code.
+// units (groupby/group_aggregate.hip, groupby_wide/group_aggregate_wide.hip, semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip,
+// arith/arith_kernels.hip, topk/top_k.hip).  No device code: kernels are only launched from here (launch_tier, launch_rowid_prefix).
 #pragma once
 
 #include <atomic>
@@ -74,6 +75,30 @@ void launch_tier(const Env &env, const Args &k, uint64_t ntiles, size_t lds, siz
     if (max_dyn > 0) allow_dynamic_lds<Kernel>(max_dyn, env.device);
     const unsigned grid = grid_for(ntiles, cap_bpc(table_bpc<Kernel>(lds, fixed_lds, env.device), env.max_blocks_per_cu), env.num_cus);
     MI355_LAUNCH(env.record, 0, Kernel, dim3(grid), dim3(kBlockThreads), lds, env.stream, k);
+}
+
+// ---- the chunk prefix over a bitmap of n rows (kernels/bitmap.hpp): the prefix part of the selection workspace, its launches ----
+struct RowidPlan {
+    uint64_t nbytes, nchunks, ngroups; // the bitmap's bytes, its chunks of kRowidChunk bytes, their scan groups
+    uint64_t words;                    // chunk counts, the total's slot, one total per scan group
+};
+inline RowidPlan rowid_plan(uint64_t n)
+{
+    RowidPlan p;
+    p.nbytes = (n + 7) / 8;
+    p.nchunks = (p.nbytes + kRowidChunk - 1) / kRowidChunk;
+    p.ngroups = rowid_scan_groups(p.nchunks);
+    p.words = rowid_prefix_words(p.nchunks);
+    return p;
+}
+// the grid of a kernel that deals a wave per chunk: eight blocks per CU at the most
+inline unsigned rowid_chunk_grid(const RowidPlan &p, int num_cus) { return grid_for(p.nchunks, 8, num_cus); }
+// rowid_scan_kernel over g's chunk counts; COUNT: rowid_count_kernel in front of it, which fills them from g's bitmap.
+// Env: LaunchEnv.
+template <bool COUNT, typename Env> void launch_rowid_prefix(const Env &env, const RowidPlan &p, const RowidArgs &g)
+{
+    if constexpr (COUNT) MI355_LAUNCH(env.record, 0, rowid_count_kernel, dim3(rowid_chunk_grid(p, env.num_cus)), dim3(256), 0, env.stream, g);
+    MI355_LAUNCH(env.record, 0, rowid_scan_kernel, dim3((unsigned)p.ngroups), dim3(256), 0, env.stream, g);
 }
 
 // ---- store policies: `scan_nt_stores` is the option (-1 = by size), `out_bytes` what the launch writes ------------------

@@ -27,7 +27,7 @@ struct LookupLaunch {
 // all of a block's LDS is dynamic: the waves' images, and the table in the LDS tier
 template <int CT> hipError_t launch_lookup(const LookupLaunch &r)
 {
-    const uint64_t ntiles = (r.k.n + kLookupTileRows - 1) / kLookupTileRows;
+    const uint64_t ntiles = rt_ntiles(r.k.n);
     const int max_dyn = (int)(lookup_images_lds(32) + kLookupLdsMaxBytes);
     if (r.in_lds)
         launch_tier<lookup_lds_kernel<CT>>(r.env, r.k, ntiles, lookup_images_lds(r.k.c) + lookup_table_lds(r.k.reach, CT), 0, max_dyn);

@@ -2,16 +2,16 @@
 // for each fact row the attribute of the dimension row its foreign key points at (GROUP BY d.attr), or a dictionary re-code.
 // gfx950 only; part of libmi355scan.so through lookup/lookup.hip.
 //
-// Pipeline.  group_aggregate_kernel's run-time-width form (groupby/group_aggregate.hpp): a wave owns tiles of 64 x 32
+// Pipeline.  The run-time-width tile stream of kernels/rt_column.hpp, packed in and packed out: a wave owns tiles of 64 x 32
 // consecutive rows, lane l rows [32 l, 32 l + 32).  The kernels are templates of the OUTPUT width CT only (32 instantiations
-// each): the lane's 32 results are 32 CT bits = exactly CT whole dwords, assembled at compile-time bit offsets (insert<CT, K>,
+// each): the lane's 32 results are 32 CT bits = exactly CT whole dwords, assembled at compile-time bit offsets (rt_insert<CT, K>,
 // the mirror of extract<C, K>) and stored at byte 4 CT lane of the tile's 256 CT output bytes -- no two lanes share a dword.
-// The input width c is a wave-uniform run-time number: the tile travels by LDS-DMA (non-temporal: the column is read once),
-// stays in LDS and is decoded from there (columns_lds_value), so a wave has two images of it and alternates -- the next tile
-// lands in one while the other is decoded.  The result dwords of a full tile leave one tile later, in front of the next DMA
-// (so no wait for a tile ever waits for a younger store), with the widest stores the lane's alignment admits: 16 bytes when
-// CT is a multiple of 4, 8 when it is even, else 4.  The ragged tile writes exactly the bytes it owns, the bits behind value
-// n - 1 of the last byte zero.
+// The input width c is a wave-uniform run-time number: the tile travels by LDS-DMA (non-temporal: the column is
+// read once; the kernel's own copy of rt_issue_tile's loop), stays in LDS and is decoded from there (columns_lds_value), so a wave has two images of it and alternates -- the
+// next tile lands in one while the other is decoded.  The result dwords of a full tile leave one tile later, in front of the next
+// DMA (so no wait for a tile ever waits for a younger store), with the widest stores the lane's alignment admits (rt_store): 16
+// bytes when CT is a multiple of 4, 8 when it is even, else 4.  The ragged tile writes exactly the bytes it owns, the bits behind
+// value n - 1 of the last byte zero (rt_store_tail).
 //
 // Bound.  reach = min(table_rows, 2^c) is what a value can address; values >= reach get `miss`.  The index is clamped
 // without a branch, so rows >= n of the ragged tile (stale LDS) form clamped addresses only:
@@ -40,7 +40,7 @@
 #pragma once
 
 #include "../kernels.hpp"
-#include "../predicates/columns.hpp" // columns_lds_value: a value of run-time width out of LDS
+#include "../kernels/rt_column.hpp" // the tile stream of a column of run-time width, and the packed-out half
 
 namespace mi355 {
 
@@ -57,16 +57,12 @@ struct LookupArgs {
     uint32_t nts;          // result stores: 0 plain, 1 non-temporal, 2 write-through (one uniform branch per tile)
 };
 
-constexpr int kLookupVpl = 32;                            // rows per lane and tile: the run-time-width decode's geometry
-constexpr int kLookupTileRows = 64 * kLookupVpl;          // 2048
 constexpr uint32_t kLookupLdsSlack = 64;                  // the dword behind the last lane's run, rounding to 16
 
-// an image of the input tile: 64 lanes x 32 rows x c bits, in whole LDS-DMA instructions
-constexpr uint32_t lookup_image(uint32_t c) { return (64u * kLookupVpl * c / 8 + 1023u) / 1024u * 1024u; }
-// the waves' images of a block; + 16: the dword behind the last lane's run is read (and not used)
-constexpr uint32_t lookup_images_lds(uint32_t c) { return kWavesPerBlock * 2u * lookup_image(c) + 16u; }
+// the waves' images of a block, two per wave; + 16: the dword behind the last lane's run is read (and not used)
+constexpr uint32_t lookup_images_lds(uint32_t c) { return kWavesPerBlock * 2u * rt_image(c) + 16u; }
 // MI355_LOOKUP_LDS_MAX_BYTES: what the widest images (c = 32) leave of a CU's LDS for the table and its `miss` entry
-constexpr uint32_t kLookupLdsMaxBytes = (kCuLdsBytes - kWavesPerBlock * 2u * lookup_image(32) - kLookupLdsSlack) & ~15u;
+constexpr uint32_t kLookupLdsMaxBytes = (kCuLdsBytes - kWavesPerBlock * 2u * rt_image(32) - kLookupLdsSlack) & ~15u;
 constexpr uint32_t lookup_entry_bytes(unsigned ct) { return ct <= 8 ? 1u : (ct <= 16 ? 2u : 4u); }
 constexpr bool lookup_in_lds(unsigned c, uint64_t table_rows, unsigned ct)
 {
@@ -77,32 +73,11 @@ constexpr uint32_t lookup_table_lds(uint32_t reach, unsigned ct) { return ((reac
 static_assert(lookup_images_lds(32) + kLookupLdsMaxBytes <= kCuLdsBytes, "LDS budget");
 static_assert(kLookupLdsMaxBytes >= (4096u + 1u) * 4u, "a 12-bit key column's whole table fits at any output width");
 
-// ---- insert: value K of a lane's run of CT-bit results into its CT output dwords, the mirror of extract<C, K> ----
-// Called for K = 0, 1, ..., 31 in this order: the first value that touches a dword assigns it (bit offset 0, or the upper
-// part of a straddling value), so the dwords need no clearing.  x < 2^CT.
-template <int CT, int K> __device__ __forceinline__ void insert(uint32_t (&w)[CT], uint32_t x)
-{
-    constexpr int bit = K * CT;
-    constexpr int d = bit >> 5;
-    constexpr int s = bit & 31;
-    if constexpr (s == 0) {
-        w[d] = x;
-    } else {
-        w[d] |= x << s; // v_lshl_or_b32
-        if constexpr (s + CT > 32) w[d + 1] = x >> (32 - s);
-    }
-}
-template <int CT, int K = 0> __device__ __forceinline__ void insert_all(uint32_t (&w)[CT], const uint32_t (&x)[kLookupVpl])
-{
-    insert<CT, K>(w, x[K]);
-    if constexpr (K + 1 < kLookupVpl) insert_all<CT, K + 1>(w, x);
-}
-
 // the lane's 32 input values out of the image (run-time width: scalar offsets)
-template <int K = 0> __device__ __forceinline__ void lookup_decode(const uint8_t *base, uint32_t c, uint32_t vmask, uint32_t (&v)[kLookupVpl])
+template <int K = 0> __device__ __forceinline__ void lookup_decode(const uint8_t *base, uint32_t c, uint32_t vmask, uint32_t (&v)[kRtVpl])
 {
     v[K] = columns_lds_value<K>(base, c, vmask);
-    if constexpr (K + 1 < kLookupVpl) lookup_decode<K + 1>(base, c, vmask, v);
+    if constexpr (K + 1 < kRtVpl) lookup_decode<K + 1>(base, c, vmask, v);
 }
 
 // ---- a value of the packed table: gather's two-dword read (extras/gather.hpp), never beyond dword last_word ----
@@ -149,69 +124,40 @@ template <int CT> __device__ __forceinline__ void lookup_stage_table(const Looku
     __syncthreads();
 }
 
-// a full tile's CT dwords of the lane: the widest stores 4 CT lane bytes of alignment admit
-template <int CT, int NT> __device__ __forceinline__ void lookup_store(uint8_t *dst, const uint32_t (&r)[CT])
-{
-    constexpr int W = CT % 4 == 0 ? 4 : (CT % 2 == 0 ? 2 : 1);
-#pragma unroll
-    for (int j = 0; j < CT; j += W) {
-        uint32_t part[W];
-#pragma unroll
-        for (int q = 0; q < W; q++) part[q] = r[j + q];
-        store_words<W, NT>(dst + 4 * j, part);
-    }
-}
-
-// the ragged tile: the lane's `valid` (0 .. 32) rows -- ceil(valid CT / 8) bytes, trailing bits of the last one zero
-template <int CT> __device__ __forceinline__ void lookup_store_tail(uint8_t *dst, const uint32_t (&r)[CT], int valid)
-{
-    const int bits = valid * CT;
-    const int nbytes = (bits + 7) / 8;
-    const int whole = nbytes / 4; // dwords written whole; dword `whole` gives the 0 .. 3 bytes left
-    uint32_t part = 0;
-#pragma unroll
-    for (int j = 0; j < CT; j++) {
-        const uint32_t v = r[j] & tail_mask(bits, j);
-        if (j < whole) ((uint32_t *)dst)[j] = v;
-        if (j == whole) part = v;
-    }
-#pragma unroll
-    for (int b = 0; b < 3; b++)
-        if (4 * whole + b < nbytes) dst[4 * whole + b] = (uint8_t)(part >> (8 * b));
-}
-
 // both tiers.  LDS_TABLE: the table is staged into the block's LDS, else read where it lies.
 template <int CT, bool LDS_TABLE> __device__ __forceinline__ void lookup_body(const LookupArgs &a)
 {
-    constexpr int VPL = kLookupVpl;
+    constexpr int VPL = kRtVpl;
     constexpr int AUX = 2; // the column is streamed once: non-temporal DMA
     constexpr uint32_t EB = lookup_entry_bytes(CT);
-    constexpr uint32_t OUT_TILE = 64u * VPL / 8u * CT; // output bytes of a tile
+    constexpr uint32_t OUT_TILE = rt_tile_bytes(CT); // output bytes of a tile
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t c = a.c;
-    const uint32_t tile_bytes = 64u * VPL / 8u * c; // a multiple of 256
-    const uint32_t image = lookup_image(c);
+    const uint32_t tile_bytes = rt_tile_bytes(c); // a multiple of 256
+    const uint32_t image = rt_image(c);
     uint8_t *cur = mi355_dyn_lds + (uint32_t)wave * 2u * image; // the image being decoded ...
     uint8_t *nxt = cur + image;                                 // ... and where the next tile lands
     uint8_t *const table_lds = mi355_dyn_lds + lookup_images_lds(c); // LDS tier: the block's decoded table, behind the images
-    const uint32_t vmask = c >= 32 ? 0xffffffffu : ((1u << c) - 1u);
+    const uint32_t vmask = rt_vmask(c);
 
     const uint64_t n = a.n;
-    const uint64_t ntiles = (n + kLookupTileRows - 1) / kLookupTileRows, nfull = n / kLookupTileRows;
+    const uint64_t ntiles = rt_ntiles(n), nfull = rt_nfull(n);
     const uint64_t data_bytes = (n * c + 7) / 8;
     const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
     uint64_t tile = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
     const uint32_t reach = a.reach, limit = a.limit, last_word = a.last_word, miss = a.miss, nts = a.nts;
 
-    // tile t of the column: LDS-DMA into `dst` (the last tile: only 16-byte chunks that start inside the payload)
+    // tile t of the column: LDS-DMA into `dst` (the last tile: only 16-byte chunks that start inside the payload).  The kernel's own
+    // copy of rt_issue_tile's loop, as its store dispatch is of store_words_by and `left` of lane_valid_rows (kernels/rt_column.hpp):
+    // with the shared forms all 64 instantiations compile to another schedule, five to other register counts
     auto issue = [&](uint64_t t, uint8_t *dst) {
         const uint64_t first = t * tile_bytes;
         const uint8_t *src = a.packed + first;
         const uint64_t left = data_bytes - first; // t < ntiles: at least one byte
         const uint32_t lim = left < tile_bytes ? (uint32_t)left : tile_bytes;
 #pragma unroll
-        for (int j = 0; j < 8; j++) { // a tile is at most 8 KiB
+        for (int j = 0; j < kRtDmaInstrs; j++) {
             const uint32_t o = j * 1024 + lane * 16;
             if ((uint32_t)j * 1024u < tile_bytes && o < lim) __builtin_amdgcn_global_load_lds(MI355_GPTR(src + o), MI355_LPTR(dst + j * 1024), 16, 0, AUX);
         }
@@ -226,11 +172,11 @@ template <int CT, bool LDS_TABLE> __device__ __forceinline__ void lookup_body(co
     auto store_prev = [&]() {
         uint8_t *dst = out_lane + prev * OUT_TILE;
         if (nts == 2)
-            lookup_store<CT, 2>(dst, res);
+            rt_store<CT, 2>(dst, res);
         else if (nts == 1)
-            lookup_store<CT, 1>(dst, res);
+            rt_store<CT, 1>(dst, res);
         else
-            lookup_store<CT, 0>(dst, res);
+            rt_store<CT, 0>(dst, res);
     };
     while (tile < ntiles) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the tile has landed
@@ -239,7 +185,7 @@ template <int CT, bool LDS_TABLE> __device__ __forceinline__ void lookup_body(co
         if (next < ntiles) issue(next, nxt);
 
         uint32_t v[VPL], x[VPL];
-        lookup_decode(cur + (uint32_t)lane * (VPL / 8u * c), c, vmask, v);
+        lookup_decode(cur + (uint32_t)lane * rt_lane_bytes(c), c, vmask, v);
         if constexpr (LDS_TABLE) {
 #pragma unroll
             for (int k = 0; k < VPL; k++) {
@@ -257,12 +203,12 @@ template <int CT, bool LDS_TABLE> __device__ __forceinline__ void lookup_body(co
 #pragma unroll
             for (int k = 0; k < VPL; k++) x[k] = v[k] > limit ? miss : t[k].value(v[k] < limit ? v[k] : limit);
         }
-        insert_all<CT>(res, x);
+        rt_insert_all<CT>(res, x);
         if (tile < nfull) {
             prev = tile;
         } else {
-            const int64_t left = (int64_t)(n - tile * kLookupTileRows) - (int64_t)lane * VPL;
-            lookup_store_tail<CT>(out_lane + tile * OUT_TILE, res, left >= VPL ? VPL : (left <= 0 ? 0 : (int)left));
+            const int64_t left = (int64_t)(n - tile * kRtTileRows) - (int64_t)lane * VPL;
+            rt_store_tail<CT>(out_lane + tile * OUT_TILE, res, left >= VPL ? VPL : (left <= 0 ? 0 : (int)left));
             prev = ~0ull;
         }
         uint8_t *const t2 = cur;

@@ -33,6 +33,7 @@
 #pragma once
 
 #include "../kernels.hpp"
+#include "../kernels/rt_column.hpp" // columns_lds_value: column 2's decode when SAME = false
 
 namespace mi355 {
 
@@ -78,14 +79,6 @@ template <bool WIDE> struct ColumnsPred {
         }
     }
 };
-
-// value `ROW` of a lane's run of run-time width c2, out of LDS: base = the lane's first byte
-template <int ROW> __device__ __forceinline__ uint32_t columns_lds_value(const uint8_t *base, uint32_t c2, uint32_t vmask2)
-{
-    const uint32_t bit = (uint32_t)ROW * c2; // wave-uniform
-    const uint32_t *p = (const uint32_t *)(base + (bit >> 5) * 4);
-    return __builtin_amdgcn_alignbit(p[1], p[0], bit & 31u) & vmask2;
-}
 
 template <int C1, int VPL, bool SAME, bool WIDE, int J, int K, int NW>
 __device__ __forceinline__ void columns_step(const uint32_t (&w1)[NW], const uint32_t (&w2)[SAME ? NW : 1], const uint8_t *base2, uint32_t c2,
@@ -169,7 +162,9 @@ template <int C1, int VPL, bool SAME, bool WIDE> __device__ __forceinline__ void
             store_words<WORDS, 0>(dst, res);
     };
 
-    // tile t of both columns, and of the mask when the tile is full: LDS-DMA into the wave's images (column 2: into `dst2`)
+    // tile t of both columns, and of the mask when the tile is full: LDS-DMA into the wave's images (column 2: into `dst2`).
+    // Kept in its own form -- the DMA loop is rt_issue_tile's, the store dispatch store_words_by's, `left` lane_valid_rows' (all
+    // kernels/rt_column.hpp): with them nine instantiations took more registers (c = 19, SAME: 128 -> 139), DESIGN.md 3.1.
     auto issue = [&](uint64_t t, uint8_t *dst2) {
         tc.template issue<AUX>(s.packed, t, lds1, lane);
         if constexpr (SAME) {

@@ -1,6 +1,6 @@
 // top_k.hip -- implementation of include/mi355_topk.h: argument checks, the selection workspace, and the launches of a call --
-// per digit topk_hist_kernel<C> and topk_pick_kernel, then topk_emit_kernel<C>, rowid_scan_kernel (kernels/bitmap.hpp, as
-// mi355_bitmap_to_rowids_dev launches it) and topk_trim_kernel<C> (topk/top_k.hpp).  Its own translation unit: neither the other
+// per digit topk_hist_kernel<C> and topk_pick_kernel, then topk_emit_kernel<C>, rowid_scan_kernel (kernels/bitmap.hpp, through
+// launch_rowid_prefix of launch_util.hpp) and topk_trim_kernel<C> (topk/top_k.hpp).  Its own translation unit: neither the other
 // entry points nor the width groups rebuild with it.  The grids come from a LaunchEnv (ctx.hpp), as in semijoin/, lookup/ and compact/.
 #include "../ctx.hpp"
 
@@ -18,6 +18,7 @@ struct TopkLaunch {
     TopkArgs k;
     TopkPickArgs pick;
     RowidArgs scan;
+    RowidPlan plan;
     LaunchEnv env;
     unsigned passes;
 };
@@ -52,7 +53,7 @@ template <int C> hipError_t launch_top_k(const TopkLaunch &r)
         MI355_LAUNCH(rec, 0, topk_pick_kernel, dim3(1), dim3(256), 0, r.env.stream, p);
     }
     MI355_LAUNCH(rec, 0, topk_emit_kernel<C>, dim3(emit_grid), dim3(kBlockThreads), 0, r.env.stream, k);
-    MI355_LAUNCH(rec, 0, rowid_scan_kernel, dim3((unsigned)((r.k.nchunks + kRowidScanGroup - 1) / kRowidScanGroup)), dim3(256), 0, r.env.stream, r.scan);
+    launch_rowid_prefix<false>(r.env, r.plan, r.scan); // topk_emit_kernel has counted the ties per chunk
     MI355_LAUNCH(rec, 0, topk_trim_kernel<C>, dim3(trim_grid), dim3(kBlockThreads), 0, r.env.stream, k);
     return hipGetLastError();
 }
@@ -87,11 +88,10 @@ int mi355_top_k_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned
         return fail(MI355_E_INVALID, "result_dev overlaps mask_dev: the mask is read while the result is written");
     if (ranges_overlap(result_dev, 4 * sizeof(uint64_t), bitmap_dev, nbytes))
         return fail(MI355_E_INVALID, "result_dev overlaps bitmap_dev");
-    // chunk counts, the total's slot, one total per scan group (the layout of mi355_bitmap_to_rowids_dev); the state; the counters
-    const uint64_t nchunks = (nbytes + kRowidChunk - 1) / kRowidChunk;
-    const uint64_t ngroups = (nchunks + kRowidScanGroup - 1) / kRowidScanGroup;
+    // the chunk prefix of the ties (launch_util.hpp rowid_plan); the state; the counters
+    const RowidPlan plan = rowid_plan(n);
+    const uint64_t nchunks = plan.nchunks, front = plan.words;
     const unsigned passes = topk_passes(c);
-    const uint64_t front = nchunks + 1 + ngroups;
     const uint64_t words = front + kTopkStateWords + (uint64_t)passes * kTopkBuckets;
     MI355_CHECK(rowid_ws_get(ctx, words, "mi355_top_k_dev"));
     unsigned long long *const ws = ctx->rowid_ws;
@@ -113,6 +113,7 @@ int mi355_top_k_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned
     r.pick.flip = r.k.flip;
     r.scan.chunk_counts = ws;
     r.scan.nchunks = nchunks;
+    r.plan = plan;
     r.passes = passes;
     r.env = launch_env(ctx);
     llc_forget(ctx);

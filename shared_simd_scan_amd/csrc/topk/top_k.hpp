@@ -40,6 +40,7 @@
 #pragma once
 
 #include "../kernels.hpp"
+#include "../kernels/rt_column.hpp" // lane_valid_rows, store_words_by
 
 namespace mi355 {
 
@@ -95,12 +96,6 @@ struct TopkPickArgs {
 
 template <int C> constexpr int topk_vpl() { return scan_vpl(C, kModeEq); }
 
-__device__ __forceinline__ unsigned long long topk_uniform(unsigned long long v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // the lane's mask words of tile t: the whole dwords of a full tile, only the bytes the bitmap is guaranteed to hold of the ragged one
 template <int C, int VPL>
 __device__ __forceinline__ void topk_load_words(const uint8_t *bits, const TileCtx<C, VPL> &tc, uint64_t t, int lane, uint32_t (&m)[VPL / 32])
@@ -122,13 +117,6 @@ __device__ __forceinline__ void topk_load_words(const uint8_t *bits, const TileC
             m[j] = v;
         }
     }
-}
-
-// rows of the lane inside the column (0..VPL) in tile t
-template <int C, int VPL> __device__ __forceinline__ int topk_valid(const TileCtx<C, VPL> &tc, uint64_t t, int lane)
-{
-    const int64_t left = (int64_t)(tc.n - t * ScanGeom<C, VPL>::TILE_VALUES) - (int64_t)lane * VPL;
-    return left >= VPL ? VPL : (left <= 0 ? 0 : (int)left);
 }
 
 // value K of the lane: one LDS atomic when its row qualifies and its higher digits are the prefix's
@@ -201,7 +189,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_hist_kern
             }
             const bool full = tile < tc.nfull;
             if (!full) { // rows behind the column count for nothing
-                const int valid = topk_valid<C, VPL>(tc, tile, lane);
+                const int valid = lane_valid_rows<VPL>(tc.n, tile, lane);
 #pragma unroll
                 for (int j = 0; j < WORDS; j++) m[j] &= tail_mask(valid, j);
             }
@@ -330,7 +318,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_emit_kern
         decode_words<C, VPL, 0, 1, kModeRange, G::LANE_DWORDS>(w, ge, range_key);
         decode_words<C, VPL, 0, 1, kModeEq, G::LANE_DWORDS>(w, eq, eq_key);
         const bool full = tile < tc.nfull;
-        const int valid = full ? VPL : topk_valid<C, VPL>(tc, tile, lane);
+        const int valid = full ? VPL : lane_valid_rows<VPL>(tc.n, tile, lane);
         uint32_t out[WORDS];
         uint32_t ties = 0;
 #pragma unroll
@@ -342,12 +330,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_emit_kern
         }
         uint8_t *const dst = a.bitmap + tile * G::BITMAP_BYTES + (uint64_t)lane * (WORDS * 4);
         if (full) {
-            if (nts == 2)
-                store_words<WORDS, 2>(dst, out);
-            else if (nts == 1)
-                store_words<WORDS, 1>(dst, out);
-            else
-                store_words<WORDS, 0>(dst, out);
+            store_words_by<WORDS>(dst, out, nts);
         } else {
             topk_store_bytes<WORDS>(dst, out, (valid + 7) / 8);
         }
@@ -370,24 +353,15 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_trim_kern
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t *lds_wave = lds[wave];
     const TileCtx<C, VPL> tc(a.n);
-    const unsigned long long r = topk_uniform(a.state[kTopkRemaining]);
+    const unsigned long long r = uniform64(a.state[kTopkRemaining]);
     const bool add = __builtin_amdgcn_readfirstlane(topk_ties_in(a) ? 0 : 1) != 0; // the ties' bits are not there yet
     const uint32_t T = __builtin_amdgcn_readfirstlane((uint32_t)a.state[kTopkPrefix] ^ a.flip);
     const uint32_t eq_key[kMaxKeysPerPass] = {T, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long *const totals = a.chunk_counts + a.nchunks + 1;
+    const ChunkPrefix ties{a.chunk_counts, a.nchunks};
     const uint64_t stride = (uint64_t)gridDim.x * kWavesPerBlock;
 
     for (uint64_t ch = (uint64_t)blockIdx.x * kWavesPerBlock + wave; ch < a.nchunks; ch += stride) {
-        // ties before this chunk = totals of the earlier scan groups + the chunk's prefix inside its group
-        const uint64_t g = ch / kRowidScanGroup;
-        unsigned long long before = 0;
-        for (uint64_t i = lane; i < g; i += 64) before += totals[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-        const unsigned long long prefix = a.chunk_counts[ch];
-        const bool last_of_group = (ch + 1) % kRowidScanGroup == 0 || ch + 1 == a.nchunks;
-        const unsigned long long count = topk_uniform((last_of_group ? totals[g] : a.chunk_counts[ch + 1]) - prefix);
-        before = topk_uniform(before + prefix);
+        const auto [before, count] = chunk_span_wave(ties, ch, lane); // the ties in front of this chunk, and its own
         // every tie of the chunk has the bit it should have: nothing of it is read
         if (count == 0 || (add ? before >= r : before + count <= r)) continue;
 
@@ -399,7 +373,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_trim_kern
             uint32_t o[WORDS], q[WORDS]; // the output's words; where a tie may be: in the output, or (adding) among the qualifying rows
             topk_load_words<C, VPL>(a.bitmap, tc, tile, lane, o);
             if (add) {
-                const int valid = topk_valid<C, VPL>(tc, tile, lane);
+                const int valid = lane_valid_rows<VPL>(tc.n, tile, lane);
 #pragma unroll
                 for (int j = 0; j < WORDS; j++) q[j] = 0xffffffffu;
                 if (a.mask) topk_load_words<C, VPL>(a.mask, tc, tile, lane, q);
@@ -428,7 +402,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_trim_kern
             uint32_t allowed = rank0 >= r ? 0u : (r - rank0 < cnt ? (uint32_t)(r - rank0) : cnt);
             if (add ? allowed > 0 : allowed < cnt) {
                 const bool full = tile < tc.nfull;
-                const int nbytes = (topk_valid<C, VPL>(tc, tile, lane) + 7) / 8;
+                const int nbytes = (lane_valid_rows<VPL>(tc.n, tile, lane) + 7) / 8;
                 uint8_t *const dst = a.bitmap + tile * G::BITMAP_BYTES + (uint64_t)lane * (WORDS * 4);
 #pragma unroll
                 for (int j = 0; j < WORDS; j++) {

@@ -362,10 +362,16 @@ def test_arith_sources_read_no_flag_bits():
 
 
 def test_arith_reuses_the_lookup_pipeline():
-    """the packed-out helpers are lookup.hpp's: included, not copied"""
+    """the tile stream and the packed-out helpers are kernels/rt_column.hpp's, which lookup.hpp includes as well: included, not
+    copied, under either name"""
     text = open(os.path.join(support.CSRC, "arith", "arith.hpp")).read()
-    assert '#include "../lookup/lookup.hpp"' in text
-    for helper in ("insert", "insert_all", "lookup_decode", "lookup_store", "lookup_store_tail", "columns_lds_value"):
+    assert '#include "../kernels/rt_column.hpp"' in text and "lookup/lookup.hpp" not in text.split("#pragma once")[1]
+    assert '#include "../kernels/rt_column.hpp"' in open(os.path.join(support.CSRC, "lookup", "lookup.hpp")).read()
+    home = open(os.path.join(support.CSRC, "kernels", "rt_column.hpp")).read()
+    for helper in ("rt_insert", "rt_insert_all", "rt_store", "rt_store_tail", "rt_issue_tile", "store_words_by", "columns_lds_value"):
+        assert re.search(rf"\bvoid\s+{helper}\s*\(|\buint32_t\s+{helper}\s*\(", home), helper
+    for helper in ("insert", "insert_all", "lookup_decode", "lookup_store", "lookup_store_tail", "columns_lds_value",
+                   "rt_insert", "rt_insert_all", "rt_store", "rt_store_tail", "store_words_by"):
         assert not re.search(rf"\bvoid\s+{helper}\s*\(|\buint32_t\s+{helper}\s*\(", text), helper
 
 

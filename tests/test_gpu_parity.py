@@ -1205,6 +1205,27 @@ def test_bitmap_consumers(O, eng, n):
     assert int(cnt.item()) == k and np.array_equal(ids.cpu().numpy()[:min(cap, k)], np.flatnonzero(x)[:cap])
 
 
+def test_bitmap_to_rowids_across_a_scan_group(eng):
+    """1025 full chunks of 16384 rows and a ragged one: two scan groups of chunk counts, so the ids of the last two chunks
+    start at the first group's total plus a prefix inside the second -- otherwise only the 1e9-row cases get there"""
+    import torch
+
+    chunk, group = 16384, 1024
+    n = 1025 * chunk + 1237
+    assert n % 8 == 5
+    first = 10_000_000_000
+    x = np.random.default_rng(1025).random(n) < 1.0 / 4096
+    assert x[: group * chunk].any() and x[group * chunk:].any()
+    x[[0, chunk - 1, chunk, group * chunk - 1, group * chunk, n - 1]] = True
+    expect = np.flatnonzero(x) + first
+    total = expect.size
+    bm = torch.from_numpy(np_bitmap(x)).cuda().clone()
+    for cap in (total, total // 3):
+        ids, cnt = eng.bitmap_to_rowids(bm, n, capacity=cap, first_row=first)
+        assert int(cnt.item()) == total
+        assert np.array_equal(ids.cpu().numpy()[:cap], expect[:cap])
+
+
 def test_scan_then_select_1e9(O, eng):
     """the full chain at BASELINE size: scan 1e9 x 9 bit -> bitmap -> row ids"""
     n, c = 1_000_000_000, 9

@@ -313,9 +313,14 @@ def test_groupby_wide_sources_read_no_flag_bits():
 def test_groupby_wide_reuses_the_pipeline():
     """the decode and the tile geometry are included, not copied; one kernel, not a template of a width"""
     text = open(os.path.join(support.CSRC, "groupby_wide", "group_aggregate_wide.hpp")).read()
-    assert '#include "../lookup/lookup.hpp"' in text and '#include "../predicates/columns.hpp"' in text
-    for helper in ("columns_lds_value", "lookup_image"):
+    assert '#include "../kernels/rt_column.hpp"' in text
+    code = text.split("#pragma once")[1]
+    assert "lookup/lookup.hpp" not in code and "predicates/columns.hpp" not in code
+    home = open(os.path.join(support.CSRC, "kernels", "rt_column.hpp")).read()
+    for helper in ("columns_lds_value", "rt_image"):
         assert helper in text and not re.search(rf"\buint32_t\s+{helper}\s*\(", text), helper
+        assert re.search(rf"\buint32_t\s+{helper}\s*\(", home), helper
+    assert "rt_issue_tile" in text and "global_load_lds" not in text  # the tiles' DMA is included too
     assert re.search(r"static __global__ __launch_bounds__\(kBlockThreads\) void group_aggregate_wide_kernel\(", text)
     assert not re.search(r"template\s*<[^>]*>\s*(static\s+)?__global__", text)
 

@@ -1,4 +1,4 @@
-"""ctypes binding of include/mi355_scan.h, include/mi355_columns.h, include/mi355_groupby.h, include/mi355_semijoin.h, include/mi355_lookup.h, include/mi355_compact.h, include/mi355_arith.h, include/mi355_groupby_wide.h and include/mi355_topk.h.  No compute happens in Python; a missing library is an error."""
+"""ctypes binding of the public headers under include/ (HEADERS).  No compute happens in Python; a missing library is an error."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,9 +14,9 @@ LAYOUT_LINEAR = 1
 GEN_MOD, GEN_SPLITMIX, GEN_INDEX = 0, 1, 2
 COMM_ID_BYTES = 128
 
-# every symbol include/mi355_scan.h declares: (name, restype, argtypes)
 _vp, _u64, _u32, _i32, _sz, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_size_t, C.c_int
-SYMBOLS = [
+HEADERS = {}  # public header under include/ -> every symbol it declares, as (name, restype, argtypes), oldest header first; lib() binds them all
+HEADERS["mi355_scan.h"] = [
     ("mi355_last_error", C.c_char_p, []),
     ("mi355_version", C.c_char_p, []),
     ("mi355_ctx_create", _int, [_int, _vp, C.POINTER(_vp)]),
@@ -83,48 +83,48 @@ SYMBOLS = [
     ("mi355_tile_values", _u64, [C.c_uint]),
 ]
 
-# every symbol include/mi355_columns.h declares (predicates that compare two columns row by row): bound by lib() as well
-COLUMN_SYMBOLS = [
+# predicates that compare two columns row by row
+HEADERS["mi355_columns.h"] = [
     ("mi355_scan_columns_dev", _int, [_vp, _vp, C.c_uint, _vp, C.c_uint, _u64, _int, C.c_int64, C.c_int64, _int, _vp, _vp, _vp]),
 ]
 
-# every symbol include/mi355_groupby.h declares (grouped aggregates over two columns): bound by lib() as well
-GROUP_SYMBOLS = [
+# grouped aggregates over two columns
+HEADERS["mi355_groupby.h"] = [
     ("mi355_group_aggregate_dev", _int, [_vp, _vp, C.c_uint, _vp, C.c_uint, _u64, _vp, _vp]),
 ]
 
-# every symbol include/mi355_semijoin.h declares (a column filtered by a device-resident bitmap set): bound by lib() as well
-SEMIJOIN_SYMBOLS = [
+# a column filtered by a device-resident bitmap set
+HEADERS["mi355_semijoin.h"] = [
     ("mi355_semijoin_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _u64, _int, _vp, _vp, _vp]),
     ("mi355_semijoin_kernel", C.c_char_p, [C.c_uint, _u64]),
 ]
 
-# every symbol include/mi355_lookup.h declares (a column mapped through a device-resident packed table): bound by lib() as well
-LOOKUP_SYMBOLS = [
+# a column mapped through a device-resident packed table
+HEADERS["mi355_lookup.h"] = [
     ("mi355_lookup_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _u64, C.c_uint, C.c_uint32, _vp]),
     ("mi355_lookup_kernel", C.c_char_p, [C.c_uint, _u64, C.c_uint]),
 ]
 
-# every symbol include/mi355_compact.h declares (the rows a bitmap selects, as a packed column): bound by lib() as well
-COMPACT_SYMBOLS = [
+# the rows a bitmap selects, as a packed column
+HEADERS["mi355_compact.h"] = [
     ("mi355_compact_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _vp, _u64, _vp]),
     ("mi355_compact_kernel", C.c_char_p, [C.c_uint]),
 ]
 
-# every symbol include/mi355_arith.h declares (a packed column computed row by row from two others): bound by lib() as well
-ARITH_SYMBOLS = [
+# a packed column computed row by row from two others
+HEADERS["mi355_arith.h"] = [
     ("mi355_arith_dev", _int, [_vp, _int, _vp, C.c_uint, _vp, C.c_uint, _u64, _i32, _i32, C.c_int64, C.c_uint, _u32, _vp, _vp]),
     ("mi355_arith_kernel", C.c_char_p, [_int, C.c_uint, C.c_uint, _i32, _i32, C.c_int64, C.c_uint]),
 ]
 
-# every symbol include/mi355_groupby_wide.h declares (grouped aggregates for keys beyond 12 bits): bound by lib() as well
-GROUP_WIDE_SYMBOLS = [
+# grouped aggregates for keys beyond 12 bits
+HEADERS["mi355_groupby_wide.h"] = [
     ("mi355_group_aggregate_wide_dev", _int, [_vp, _vp, C.c_uint, _vp, C.c_uint, _u64, _vp, _u64, _vp, _vp]),
     ("mi355_group_wide_front_slots", _u32, [C.c_uint, C.c_uint]),
 ]
 
-# every symbol include/mi355_topk.h declares (the k largest or smallest rows of a column, as a bitmap): bound by lib() as well
-TOPK_SYMBOLS = [
+# the k largest or smallest rows of a column, as a bitmap
+HEADERS["mi355_topk.h"] = [
     ("mi355_top_k_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _u64, _int, _vp, _vp]),
     ("mi355_top_k_passes", C.c_uint, [C.c_uint]),
 ]
@@ -148,7 +148,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the HIP extension is not built (run `python -m shared_simd_scan_amd.build`). "
                 "There is no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS + COLUMN_SYMBOLS + GROUP_SYMBOLS + SEMIJOIN_SYMBOLS + LOOKUP_SYMBOLS + COMPACT_SYMBOLS + ARITH_SYMBOLS + GROUP_WIDE_SYMBOLS + TOPK_SYMBOLS:
+        for name, res, args in sum(HEADERS.values(), []):
             fn = getattr(L, name)  # AttributeError if the library does not export what the header declares
             fn.restype = res
             fn.argtypes = args

@@ -72,11 +72,9 @@ int mi355_arith_dev(mi355_ctx *ctx, int op, const void *packed1_dev, unsigned c1
         MI355_CHECK(check_dev(packed2_dev, 16, "packed2_dev"));
         MI355_CHECK(check_dev(out_dev, 16, "out_dev"));
     }
-    const uint64_t out_bytes = (n * co + 7) / 8;
-    if (ranges_overlap(out_dev, out_bytes, packed1_dev, (n * c1 + 7) / 8))
-        return fail(MI355_E_INVALID, "out_dev overlaps packed1_dev: the column is read while the result is written");
-    if (ranges_overlap(out_dev, out_bytes, packed2_dev, (n * c2 + 7) / 8))
-        return fail(MI355_E_INVALID, "out_dev overlaps packed2_dev: the column is read while the result is written");
+    const uint64_t out_bytes = packed_bytes(n, co);
+    MI355_CHECK(check_no_overlap(out_dev, out_bytes, "out_dev", packed1_dev, packed_bytes(n, c1), "packed1_dev", "column"));
+    MI355_CHECK(check_no_overlap(out_dev, out_bytes, "out_dev", packed2_dev, packed_bytes(n, c2), "packed2_dev", "column"));
     // the counter starts from 0: all the exact kernel and an empty column leave in it
     if (out_of_range_dev) HIP_TRY(hipMemsetAsync(out_of_range_dev, 0, sizeof(uint64_t), ctx->stream));
     if (n == 0) return MI355_OK;

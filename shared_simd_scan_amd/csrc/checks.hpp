@@ -72,12 +72,21 @@ inline int check_some_output(const void *bitmap_dev, const void *hits_dev)
 }
 
 inline size_t bitmap_bytes(uint64_t n) { return (size_t)((n + 7) / 8); }
+inline uint64_t packed_bytes(uint64_t n, unsigned c) { return (n * c + 7) / 8; } // n values of c bits (n c wraps only beyond what memory holds)
 
 // do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (an output that overlaps an input a kernel reads while it writes)
 inline bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
 {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return a_bytes && b_bytes && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+// an output must not share a byte with an input that the kernel reads while it writes (`what`: the column, the table, ...)
+inline int check_no_overlap(const void *out, uint64_t out_bytes, const char *out_name, const void *in, uint64_t in_bytes, const char *in_name, const char *what)
+{
+    if (ranges_overlap(out, out_bytes, in, in_bytes))
+        return fail(MI355_E_INVALID, "%s overlaps %s: the %s is read while the result is written", out_name, in_name, what);
+    return MI355_OK;
 }
 
 // the per-predicate layout puts bitmap k at out_dev + k * stride_bytes: every one of them 16-byte aligned and long enough

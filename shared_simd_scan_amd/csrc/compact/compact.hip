@@ -50,10 +50,8 @@ int mi355_compact_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
         MI355_CHECK(check_ptr(out_dev, "out_dev"));
         const uint64_t most = capacity < n ? capacity : n;          // values the call can write
         const uint64_t out_bytes = ((most * c + 31) / 32) * 4;      // in whole dwords
-        if (ranges_overlap(out_dev, out_bytes, packed_dev, (n * c + 7) / 8))
-            return fail(MI355_E_INVALID, "out_dev overlaps packed_dev: the column is read while the result is written");
-        if (ranges_overlap(out_dev, out_bytes, bitmap_dev, bitmap_bytes(n)))
-            return fail(MI355_E_INVALID, "out_dev overlaps bitmap_dev: the bitmap is read while the result is written");
+        MI355_CHECK(check_no_overlap(out_dev, out_bytes, "out_dev", packed_dev, packed_bytes(n, c), "packed_dev", "column"));
+        MI355_CHECK(check_no_overlap(out_dev, out_bytes, "out_dev", bitmap_dev, bitmap_bytes(n), "bitmap_dev", "bitmap"));
     }
     // counts and prefix: the chunk prefix over the bitmap (launch_util.hpp rowid_plan)
     const RowidPlan p = rowid_plan(n);
@@ -73,7 +71,7 @@ int mi355_compact_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
     r.k.out = (uint32_t *)out_dev;
     r.k.capacity = capacity;
     r.k.c = c;
-    r.k.nts = (uint32_t)one_pass_store_policy(((capacity < n ? capacity : n) * c + 7) / 8, ctx->scan_nt_stores);
+    r.k.nts = (uint32_t)one_pass_store_policy(packed_bytes(capacity < n ? capacity : n, c), ctx->scan_nt_stores);
     r.env = launch_env(ctx);
     llc_forget(ctx);
     std::string *const rec = r.env.record;

@@ -1,8 +1,6 @@
 // ctx.hpp -- the context object behind include/mi355_scan.h and what every host-side translation unit of libmi355scan.so
-// shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip, groupby/group_aggregate.hip,
-// semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip, arith/arith.hip, arith/arith_kernels.hip,
-// groupby_wide/group_aggregate_wide.hip and topk/top_k.hip):
-// error reporting, the entry prologue, the context's buffers.
+// shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip and the feature units of the
+// Makefile's FEATURES table): error reporting, the entry prologue, the context's buffers.
 #pragma once
 
 #include "../../include/mi355_scan.h"
@@ -157,8 +155,8 @@ int upload_list(mi355_ctx *ctx, const void *src, size_t elem_bytes, unsigned P, 
 // CUs the persistent grids are sized for (option "grid_cus")
 inline int grid_cus(const mi355_ctx *ctx) { return ctx->grid_cus > 0 ? ctx->grid_cus : ctx->num_cus; }
 
-// What a launcher outside the width groups (groupby/, groupby_wide/, semijoin/, lookup/, compact/, arith/, topk/) takes from its context; the groups' LaunchReq has the
-// same five among its fields (capi.hip fill_common).
+// What a launcher outside the width groups (a feature unit of the Makefile's FEATURES table) takes from its context; the groups'
+// LaunchReq has the same five among its fields (capi.hip fill_common).
 struct LaunchEnv {
     hipStream_t stream;
     int device, num_cus, max_blocks_per_cu; // num_cus: grid_cus(); max_blocks_per_cu: 0 = no cap

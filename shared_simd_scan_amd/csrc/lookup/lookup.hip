@@ -61,11 +61,9 @@ int mi355_lookup_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
     if (n == 0) return MI355_OK;
     MI355_CHECK(check_ptr(packed_dev, "packed_dev"));
     MI355_CHECK(check_ptr(out_dev, "out_dev"));
-    const uint64_t out_bytes = (n * ct + 7) / 8;
-    if (ranges_overlap(out_dev, out_bytes, packed_dev, (n * c + 7) / 8))
-        return fail(MI355_E_INVALID, "out_dev overlaps packed_dev: the column is read while the result is written");
-    if (table_dev && ranges_overlap(out_dev, out_bytes, table_dev, (table_rows * ct + 7) / 8))
-        return fail(MI355_E_INVALID, "out_dev overlaps table_dev: the table is read while the result is written");
+    const uint64_t out_bytes = packed_bytes(n, ct);
+    MI355_CHECK(check_no_overlap(out_dev, out_bytes, "out_dev", packed_dev, packed_bytes(n, c), "packed_dev", "column"));
+    if (table_dev) MI355_CHECK(check_no_overlap(out_dev, out_bytes, "out_dev", table_dev, packed_bytes(table_rows, ct), "table_dev", "table"));
     const uint64_t reach = value_reach(c, table_rows); // what a c-bit value can address of the table
     LookupLaunch r{};
     r.k.packed = (const uint8_t *)packed_dev;

@@ -77,15 +77,12 @@ int mi355_top_k_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned
     }
     MI355_CHECK(check_ptr(packed_dev, "packed_dev"));
     MI355_CHECK(check_ptr(bitmap_dev, "bitmap_dev"));
-    const uint64_t nbytes = bitmap_bytes(n), col_bytes = (n * c + 7) / 8; // (n c wraps only beyond what memory holds)
-    if (ranges_overlap(bitmap_dev, nbytes, packed_dev, col_bytes))
-        return fail(MI355_E_INVALID, "bitmap_dev overlaps packed_dev: the column is read while the result is written");
+    const uint64_t nbytes = bitmap_bytes(n), col_bytes = packed_bytes(n, c);
+    MI355_CHECK(check_no_overlap(bitmap_dev, nbytes, "bitmap_dev", packed_dev, col_bytes, "packed_dev", "column"));
     if (mask_dev && bitmap_dev != mask_dev && ranges_overlap(bitmap_dev, nbytes, mask_dev, nbytes))
         return fail(MI355_E_INVALID, "bitmap_dev overlaps mask_dev without being it: only bitmap_dev == mask_dev works in place");
-    if (ranges_overlap(result_dev, 4 * sizeof(uint64_t), packed_dev, col_bytes))
-        return fail(MI355_E_INVALID, "result_dev overlaps packed_dev: the column is read while the result is written");
-    if (ranges_overlap(result_dev, 4 * sizeof(uint64_t), mask_dev, mask_dev ? nbytes : 0))
-        return fail(MI355_E_INVALID, "result_dev overlaps mask_dev: the mask is read while the result is written");
+    MI355_CHECK(check_no_overlap(result_dev, 4 * sizeof(uint64_t), "result_dev", packed_dev, col_bytes, "packed_dev", "column"));
+    MI355_CHECK(check_no_overlap(result_dev, 4 * sizeof(uint64_t), "result_dev", mask_dev, mask_dev ? nbytes : 0, "mask_dev", "mask"));
     if (ranges_overlap(result_dev, 4 * sizeof(uint64_t), bitmap_dev, nbytes))
         return fail(MI355_E_INVALID, "result_dev overlaps bitmap_dev");
     // the chunk prefix of the ties (launch_util.hpp rowid_plan); the state; the counters

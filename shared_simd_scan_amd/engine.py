@@ -139,22 +139,25 @@ def lookup_kernel(c: int, table_rows: int, ct: int) -> str:
     return _table_kernel(lambda: lib().mi355_lookup_kernel(c, int(table_rows), ct), table_rows, (c, table_rows, ct))
 
 
+def _width_query(symbol: str, *widths: int):
+    """what the library's `symbol` answers for bit widths: a width outside 0..2^32 (ctypes would wrap it) or an answer of NULL
+    or 0 (a width the library does not have) -> ValueError(the width, or the tuple of them)"""
+    answer = getattr(lib(), symbol)(*widths) if all(0 <= int(w) < 1 << 32 for w in widths) else None
+    if not answer:
+        raise ValueError(widths[0] if len(widths) == 1 else widths)
+    return answer
+
+
 def compact_kernel(c: int) -> str:
     """kernel ScanEngine.compact launches to write its values at width c (mi355_compact_kernel; arithmetic only, needs no
     device): 'compact_kernel'; a width outside 1..32 -> ValueError"""
-    s = lib().mi355_compact_kernel(c) if 0 <= int(c) < 1 << 32 else None
-    if s is None:
-        raise ValueError(c)
-    return s.decode()
+    return _width_query("mi355_compact_kernel", c).decode()
 
 
 def top_k_passes(c: int) -> int:
     """histogram passes over the column ScanEngine.top_k makes at width c, before the one that writes the bitmap
     (mi355_top_k_passes; arithmetic only, needs no device): 1 | 2 | 3; a width outside 1..32 -> ValueError"""
-    p = lib().mi355_top_k_passes(c) if 0 <= int(c) < 1 << 32 else 0
-    if not p:
-        raise ValueError(c)
-    return int(p)
+    return int(_width_query("mi355_top_k_passes", c))
 
 
 GROUP_WIDE_MAX_GROUPS = 1 << 26  # MI355_GROUP_WIDE_MAX_GROUPS
@@ -163,10 +166,7 @@ GROUP_WIDE_MAX_GROUPS = 1 << 26  # MI355_GROUP_WIDE_MAX_GROUPS
 def group_wide_front_slots(ck: int, cv: int) -> int:
     """slots of the LDS front a block of ScanEngine.group_aggregate_wide keeps at key width ck and value width cv
     (mi355_group_wide_front_slots; arithmetic only, needs no device): 4096 | 2048 | 1024; a width outside 1..32 -> ValueError"""
-    s = lib().mi355_group_wide_front_slots(ck, cv) if 0 <= int(ck) < 1 << 32 and 0 <= int(cv) < 1 << 32 else 0
-    if not s:
-        raise ValueError((ck, cv))
-    return int(s)
+    return int(_width_query("mi355_group_wide_front_slots", ck, cv))
 
 
 ARITH_OPS = {"linear": 0, "mul": 1}  # MI355_ARITH_LINEAR, MI355_ARITH_MUL
@@ -222,6 +222,20 @@ def arith_width(op: str, c1: int, c2: int, a: int = 1, b: Optional[int] = None, 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     """an optional tensor as a pointer argument: None travels as NULL"""
     return t.data_ptr() if t is not None else None
+
+
+def _col_ptr(col: "PackedColumn") -> Optional[int]:
+    """a column's data as a pointer argument: an empty column travels as NULL"""
+    return col.data.data_ptr() if col.n else None
+
+
+def _unsigned(x: int, limit: int, message: str) -> int:
+    """an int on its way to an unsigned C argument -> int(x) where 0 <= x < limit, else ValueError(message, the value in the
+    place of its {}): ctypes would wrap it silently"""
+    x = int(x)
+    if not 0 <= x < limit:
+        raise ValueError(message.format(x))
+    return x
 
 
 class PackedColumn:
@@ -290,6 +304,18 @@ class ScanEngine:
     def _empty(self, nbytes: int, dtype=torch.uint8) -> torch.Tensor:
         return torch.empty(nbytes, dtype=dtype, device=self._dev)
 
+    def _int64(self, k: int = 1) -> torch.Tensor:
+        """a device result of k counters"""
+        return self._empty(k, torch.int64)
+
+    def _packed_out(self, out: Optional[torch.Tensor], c: int, n: int, need: int) -> torch.Tensor:
+        """the buffer of a packed result of n values of c bits: allocated with the stream format's pad when None, else checked
+        against the `need` bytes the call writes at most"""
+        if out is None:
+            return self._empty(compressed_buffer_size(c, n))
+        assert out.dtype == torch.uint8 and out.numel() >= need
+        return out
+
     def alloc_packed(self, n: int, c: int) -> PackedColumn:
         return PackedColumn(self._empty(compressed_buffer_size(c, n)), n, c)
 
@@ -342,7 +368,7 @@ class ScanEngine:
         elif bitmap is None:
             bitmap = self.alloc_bitmap(n)
         if hits is None:
-            hits = torch.empty(1, dtype=torch.int64, device=self._dev)
+            hits = self._int64()
         return bitmap, hits
 
     def scan(self, key: int, col: PackedColumn, bitmap: Optional[torch.Tensor] = None,
@@ -412,8 +438,7 @@ class ScanEngine:
                     mask_op: str = "and", first_row: int = 0):
         """predicate (optionally combined with an earlier bitmap) -> (int64 ascending row ids [capacity], count int64[1])
         in one launch, no bitmap in HBM; ids beyond `capacity` are dropped, count is the total."""
-        rowids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self._dev)
-        count = torch.empty(1, dtype=torch.int64, device=self._dev)
+        rowids, count = self._int64(max(capacity, 1)), self._int64()
         check(lib().mi355_scan_select_dev(self._ctx, col.data.data_ptr(), col.n, col.c, self._CMP[op], clamp_const(a), clamp_const(b),
                                           self._BOP[mask_op], _ptr(mask), first_row,
                                           rowids.data_ptr(), capacity, count.data_ptr()))
@@ -437,9 +462,7 @@ class ScanEngine:
         `dim`, consumed where it lies (uint8 device tensor of at least ceil(set_bits/8) bytes; None only with set_bits == 0).
         Capturable into a graph: the set is read at every replay.  bitmap=False: count only, no bitmap is stored (returns
         (None, hits)); want_hits=False: no count (returns (bitmap, None))."""
-        set_bits = int(set_bits)
-        if not 0 <= set_bits <= 1 << 32:
-            raise ValueError(f"set_bits {set_bits} outside 0..2^32")  # (ctypes would wrap it silently)
+        set_bits = _unsigned(set_bits, (1 << 32) + 1, "set_bits {} outside 0..2^32")
         if set_bitmap is None:
             assert set_bits == 0
         else:
@@ -448,7 +471,7 @@ class ScanEngine:
         assert not (count_only and not want_hits), "neither a bitmap nor a count asked for"
         if bitmap is None:
             bitmap = self.alloc_bitmap(col.n)
-        hits = torch.empty(1, dtype=torch.int64, device=self._dev) if want_hits else None
+        hits = self._int64() if want_hits else None
         check(lib().mi355_semijoin_dev(self._ctx, col.data.data_ptr(), col.n, col.c, _ptr(set_bitmap),
                                        set_bits, 1 if negate else 0, _ptr(and_mask),
                                        None if count_only else bitmap.data_ptr(), _ptr(hits)))
@@ -459,15 +482,9 @@ class ScanEngine:
         fact row the attribute of the dimension row its key points at (then `group_aggregate` by it, or any scan over it), or
         a dictionary re-code.  `out`: a uint8 device tensor of at least compressed_buffer_size(table.c, col.n) bytes that
         overlaps neither input (allocated when None).  Capturable into a graph: the table is read at every replay."""
-        miss = int(miss)
-        if not 0 <= miss < 1 << table.c:
-            raise ValueError(f"miss {miss} is no value of {table.c} bits")  # (ctypes would wrap it silently)
-        if out is None:
-            out = torch.empty(compressed_buffer_size(table.c, col.n), dtype=torch.uint8, device=self._dev)
-        else:
-            assert out.dtype == torch.uint8 and out.numel() >= (col.n * table.c + 7) // 8
-        check(lib().mi355_lookup_dev(self._ctx, col.data.data_ptr(), col.n, col.c, table.data.data_ptr() if table.n else None, table.n,
-                                     table.c, miss, out.data_ptr()))
+        miss = _unsigned(miss, 1 << table.c, f"miss {{}} is no value of {table.c} bits")
+        out = self._packed_out(out, table.c, col.n, (col.n * table.c + 7) // 8)
+        check(lib().mi355_lookup_dev(self._ctx, col.data.data_ptr(), col.n, col.c, _col_ptr(table), table.n, table.c, miss, out.data_ptr()))
         return PackedColumn(out, col.n, table.c)
 
     def arith(self, op: str, col1: PackedColumn, col2: PackedColumn, a: int = 1, b: Optional[int] = None, k: int = 0,
@@ -489,12 +506,8 @@ class ScanEngine:
         co, miss = int(co), int(miss)
         if not 1 <= co <= 32:
             raise ValueError(f"co {co} outside 1..32")
-        if not 0 <= miss < 1 << co:
-            raise ValueError(f"miss {miss} is no value of {co} bits")  # (ctypes would wrap it silently)
-        if out is None:
-            out = torch.empty(compressed_buffer_size(co, col1.n), dtype=torch.uint8, device=self._dev)
-        else:
-            assert out.dtype == torch.uint8 and out.numel() >= (col1.n * co + 7) // 8
+        miss = _unsigned(miss, 1 << co, f"miss {{}} is no value of {co} bits")
+        out = self._packed_out(out, co, col1.n, (col1.n * co + 7) // 8)
         if out_of_range is not None:
             assert out_of_range.dtype == torch.int64 and out_of_range.numel() >= 1
         check(lib().mi355_arith_dev(self._ctx, code, col1.data.data_ptr(), col1.c, col2.data.data_ptr(), col2.c, col1.n, a, b, k, co, miss,
@@ -512,16 +525,11 @@ class ScanEngine:
         bitmap_to_rowids -> gather -> compress at density 1/2 (4.2 x / 2.3 x) and on clustered selections, 1.49 x / on par at
         1/8; at the measured densities 1/64 and 1/512 that route is the faster one (1.5-2 x and 2.7-3.5 x): it never reads the
         unselected rows."""
-        capacity = col.n if capacity is None else int(capacity)
-        if not 0 <= capacity < 1 << 64:
-            raise ValueError(f"capacity {capacity}")  # (ctypes would wrap it silently)
+        capacity = _unsigned(col.n if capacity is None else capacity, 1 << 64, "capacity {}")
         assert bitmap.dtype == torch.uint8 and bitmap.numel() >= (col.n + 7) // 8
-        if out is None:
-            out = torch.empty(compressed_buffer_size(col.c, capacity), dtype=torch.uint8, device=self._dev)
-        else:
-            assert out.dtype == torch.uint8 and out.numel() >= (capacity * col.c + 31) // 32 * 4
-        count = torch.empty(1, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_compact_dev(self._ctx, col.data.data_ptr() if col.n else None, col.n, col.c, bitmap.data_ptr() if col.n else None,
+        out = self._packed_out(out, col.c, capacity, (capacity * col.c + 31) // 32 * 4)  # whole dwords
+        count = self._int64()
+        check(lib().mi355_compact_dev(self._ctx, _col_ptr(col), col.n, col.c, bitmap.data_ptr() if col.n else None,
                                       out.data_ptr() if capacity else None, capacity, count.data_ptr()))
         return out, count
 
@@ -541,9 +549,7 @@ class ScanEngine:
         Capturable into a graph after a warm-up call of at least this size; column and mask are read at every replay.  Measured
         (profiles/r13_top_k.txt, uniform values): 1e9 x 9 bit 0.71-0.84 ms against 38.7 ms for decompress -> torch.topk, 2.5e8 x 32 bit
         0.86-0.91 ms against 11.7 ms; an all-equal 1e9 x 9 bit column at k = n / 2 takes 3.83 ms."""
-        k = int(k)
-        if not 0 <= k < 1 << 64:
-            raise ValueError(f"k {k}")  # (ctypes would wrap it silently)
+        k = _unsigned(k, 1 << 64, "k {}")
         nbytes = (col.n + 7) // 8
         if mask is not None:
             assert mask.dtype == torch.uint8 and mask.numel() >= nbytes
@@ -551,8 +557,8 @@ class ScanEngine:
             out = self.alloc_bitmap(col.n)
         else:
             assert out.dtype == torch.uint8 and out.numel() >= nbytes
-        result = torch.empty(4, dtype=torch.int64, device=self._dev)
-        check(lib().mi355_top_k_dev(self._ctx, col.data.data_ptr() if col.n else None, col.n, col.c, _ptr(mask) if col.n else None, k,
+        result = self._int64(4)
+        check(lib().mi355_top_k_dev(self._ctx, _col_ptr(col), col.n, col.c, _ptr(mask) if col.n else None, k,
                                     1 if largest else 0, out.data_ptr() if col.n else None, result.data_ptr()))
         return out, result
 
@@ -569,20 +575,19 @@ class ScanEngine:
     def bitmap_combine(self, op: str, a: torch.Tensor, b: torch.Tensor, n: int, out: Optional[torch.Tensor] = None):
         if out is None:
             out = self.alloc_bitmap(n)
-        count = torch.empty(1, dtype=torch.int64, device=self._dev)
+        count = self._int64()
         check(lib().mi355_bitmap_combine_dev(self._ctx, self._BOP[op], a.data_ptr(), b.data_ptr(), out.data_ptr(), n,
                                              count.data_ptr()))
         return out, count
 
     def bitmap_count(self, bitmap: torch.Tensor, n: int) -> torch.Tensor:
-        count = torch.empty(1, dtype=torch.int64, device=self._dev)
+        count = self._int64()
         check(lib().mi355_bitmap_count_dev(self._ctx, bitmap.data_ptr(), n, count.data_ptr()))
         return count
 
     def bitmap_to_rowids(self, bitmap: torch.Tensor, n: int, capacity: int, first_row: int = 0):
         """-> (int64 row ids [capacity], count int64[1]); ids beyond `capacity` are dropped, count is the total."""
-        rowids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self._dev)
-        count = torch.empty(1, dtype=torch.int64, device=self._dev)
+        rowids, count = self._int64(max(capacity, 1)), self._int64()
         check(lib().mi355_bitmap_to_rowids_dev(self._ctx, bitmap.data_ptr(), n, first_row, rowids.data_ptr(), capacity,
                                                count.data_ptr()))
         return rowids, count
@@ -595,7 +600,7 @@ class ScanEngine:
         if not torch.is_tensor(count):
             count = torch.tensor([int(count)], dtype=torch.int64, device=self._dev)
         if out is None:
-            out = torch.empty(max(cap, 1), dtype=torch.int32, device=self._dev)
+            out = self._empty(max(cap, 1), torch.int32)
         assert rowids.dtype == torch.int64 and out.dtype == torch.int32 and out.numel() >= cap
         check(lib().mi355_gather_dev(self._ctx, col.data.data_ptr(), col.n, col.c, first_row, rowids.data_ptr(), count.data_ptr(), cap,
                                      out.data_ptr()))
@@ -605,7 +610,7 @@ class ScanEngine:
         """-> int64[4] device tensor (sum, count, min, max) of the column's values over the rows of `mask` (a result bitmap;
         None = every row): one pass over the column, nothing decoded to memory.  count = 0: min is -1 (UINT64_MAX)."""
         if out is None:
-            out = torch.empty(4, dtype=torch.int64, device=self._dev)
+            out = self._int64(4)
         check(lib().mi355_aggregate_dev(self._ctx, col.data.data_ptr(), col.n, col.c, _ptr(mask), out.data_ptr()))
         return out
 
@@ -644,7 +649,7 @@ class ScanEngine:
         2^20 groups 22 ms, 2.47 x / 2.16 x as fast as decompress x 2 -> torch index_add_ / bincount / scatter_reduce_, and bound by
         its global atomics, not its bytes; 14.6 ms with half of the rows in one key, 2.2 ms on sorted keys; at 4096 groups 51 ms
         where `group_aggregate` takes 0.5 ms -- up to 12 bits use that."""
-        assert keys.n == values.n
+        assert keys.n == values.n  # (so the two column pointers below are NULL together, for the empty column)
         groups = int(groups)
         if not 1 <= groups <= min(1 << keys.c, GROUP_WIDE_MAX_GROUPS):
             raise ValueError(f"groups {groups} outside 1..min(2^{keys.c}, 2^26)")  # (ctypes would wrap a negative count silently)
@@ -653,8 +658,7 @@ class ScanEngine:
         assert tuple(out.shape) == (groups, 4) and out.dtype == torch.int64 and out.is_contiguous()
         if dropped is not None:
             assert dropped.dtype == torch.int64 and dropped.numel() >= 1
-        check(lib().mi355_group_aggregate_wide_dev(self._ctx, keys.data.data_ptr() if keys.n else None, keys.c,
-                                                   values.data.data_ptr() if keys.n else None, values.c, keys.n, _ptr(mask), groups,
+        check(lib().mi355_group_aggregate_wide_dev(self._ctx, _col_ptr(keys), keys.c, _col_ptr(values), values.c, keys.n, _ptr(mask), groups,
                                                    out.data_ptr(), _ptr(dropped)))
         return out
 
@@ -662,7 +666,7 @@ class ScanEngine:
     def _shared_outputs(self, n: int, P: int, layout: str, out, hits):
         """the outputs of a shared scan of P keys / predicates by layout -> (out, hits, hits pointer, layout code, stride)"""
         if hits is None:
-            hits = torch.empty(P, dtype=torch.int64, device=self._dev)
+            hits = self._int64(P)
         hits_ptr = 0 if hits is False else hits.data_ptr()  # hits=False: bitmaps only, no counting
         if layout == "per_predicate":
             stride = int(lib().mi355_bitmap_stride(n))  # whole 128-byte lines per bitmap: up to 2x faster than a 16-byte-multiple stride

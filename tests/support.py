@@ -63,9 +63,14 @@ def check_header_is_plain_c99(header):
                    check=True)
 
 
-def check_header_binds(L, header, symbols, earlier_headers, earlier_symbols):
-    """`header` declares exactly what the _capi list `symbols` binds, the loaded library carries those argument types, and neither
-    an earlier header nor an earlier list knows any of the names -> (names, {name: argtypes})"""
+def check_header_binds(L, header):
+    """`header` declares exactly what its list in _capi.HEADERS binds, the loaded library carries those argument types, and neither
+    an earlier header nor an earlier list (what precedes it in HEADERS) knows any of the names -> (names, {name: argtypes})"""
+    from shared_simd_scan_amd._capi import HEADERS
+
+    symbols = HEADERS[header]
+    earlier_headers = list(HEADERS)[:list(HEADERS).index(header)]
+    earlier_symbols = [s for h in earlier_headers for s in HEADERS[h]]
     names = declared(header)
     assert names == sorted(s[0] for s in symbols)
     sigs = dict((s[0], s[2]) for s in symbols)
@@ -97,7 +102,7 @@ class RecordingLib:
         self.calls = []
         if real is not None:
             self.mi355_compressed_buffer_size = real.mi355_compressed_buffer_size
-        self._sig = {name: args for name, _, args in _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS + _capi.LOOKUP_SYMBOLS}
+        self._sig = {name: args for symbols in _capi.HEADERS.values() for name, _, args in symbols}
 
     def __getattr__(self, name):
         argtypes = self._sig[name]
@@ -133,8 +138,13 @@ def fake_engine(monkeypatch, rec):
 
 
 @pytest.fixture
-def fake(monkeypatch):
-    return fake_engine(monkeypatch, RecordingLib())
+def fake(monkeypatch, L):
+    """fake_engine over a RecordingLib whose buffer-size arithmetic is the real library's, with a PackedColumn that takes any tensor
+    (the real one wants a device tensor)"""
+    from shared_simd_scan_amd import engine
+
+    monkeypatch.setattr(engine, "PackedColumn", lambda data, n, c: types.SimpleNamespace(data=data, n=int(n), c=int(c)))
+    return fake_engine(monkeypatch, RecordingLib(L))
 
 
 # ---- GPU cases ----------------------------------------------------------------------------------------------------------------

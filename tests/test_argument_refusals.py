@@ -169,12 +169,12 @@ ROW_IDS = [f"{sym[6:]}-{what.replace(' ', '_')}" for sym, what, _, _ in ROWS]
 
 
 def test_row_ids_unique_and_every_dev_symbol_has_rows():
-    from shared_simd_scan_amd._capi import COLUMN_SYMBOLS, SYMBOLS
+    from shared_simd_scan_amd._capi import HEADERS
 
     assert len(set(ROW_IDS)) == len(ROW_IDS)
-    dev = {name for name, _, _ in SYMBOLS + COLUMN_SYMBOLS if name.endswith("_dev")}
+    dev = {name for name, _, _ in HEADERS["mi355_scan.h"] + HEADERS["mi355_columns.h"] if name.endswith("_dev")}
     assert dev - EXCLUDED == set(CALLS) == {sym for sym, _, _, _ in ROWS}
-    assert EXCLUDED <= {name for name, _, _ in SYMBOLS}
+    assert EXCLUDED <= {name for name, _, _ in HEADERS["mi355_scan.h"]}
 
 
 class Arena:

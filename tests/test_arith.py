@@ -1,7 +1,7 @@
 """A packed column computed row by row from two others (include/mi355_arith.h, ScanEngine.arith):
 out[i] = r_i if 0 <= r_i < 2^co else miss, with r_i = a x_i + b y_i + k ("linear") or a x_i y_i + k ("mul"), packed in and out.
 
-CPU: the header is plain C99 and declares exactly what _capi.ARITH_SYMBOLS binds and the library exports; it carries its
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports; it carries its
 graph-capture verdict; mi355_arith_kernel (pure arithmetic) names the kernel at every boundary of the range rule and refuses what
 the call refuses; arith_range equals a brute force over all inputs at widths <= 4; the co=None rule; arith hands the C ABI what it
 should (through a recording stand-in for the library); without a device the entry point fails with a message; every __global__
@@ -21,13 +21,12 @@ import functools
 import itertools
 import os
 import re
-import types
 
 import numpy as np
 import pytest
 
 import support
-from support import L, RecordingLib, eng, hostile_pack, plain_pack, record  # noqa: F401  (L, eng: fixtures)
+from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 from test_kernel_paths import SENTINEL, Guarded, base_name, parse_record
 from test_lookup import corner_rows, grouped
 
@@ -169,11 +168,7 @@ def test_arith_header_is_plain_c99():
 
 
 def test_arith_header_declares_what_python_binds(L):
-    from shared_simd_scan_amd import _capi
-
-    names, sigs = support.check_header_binds(
-        L, HEADER, _capi.ARITH_SYMBOLS, ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h", "mi355_lookup.h", "mi355_compact.h"),
-        _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS + _capi.LOOKUP_SYMBOLS + _capi.COMPACT_SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert names == ["mi355_arith_dev", "mi355_arith_kernel"]
     sig = sigs["mi355_arith_dev"]
     assert sig[1] is C.c_int and sig[3] is C.c_uint and sig[5] is C.c_uint and sig[6] is C.c_uint64 and sig[7] is C.c_int32 and sig[8] is C.c_int32
@@ -282,17 +277,6 @@ def test_default_width_is_the_smallest_that_holds_hi():
     for bad in (("linear", 9, 9, 1, -1, 510), ("linear", 31, 31, 1, 1, 2), ("mul", 17, 16), ("linear", 9, 9, 1, 1, -1)):
         with pytest.raises(ValueError):  # lo < 0, or hi >= 2^32
             arith_width(*bad)
-
-
-@pytest.fixture
-def fake(monkeypatch, L):
-    """support.fake with the real buffer-size arithmetic, the new signatures, and a PackedColumn that takes any tensor"""
-    from shared_simd_scan_amd import _capi, engine
-
-    monkeypatch.setattr(engine, "PackedColumn", lambda data, n, c: types.SimpleNamespace(data=data, n=int(n), c=int(c)))
-    rec = RecordingLib(L)
-    rec._sig.update({name: args for name, _, args in _capi.ARITH_SYMBOLS})
-    return support.fake_engine(monkeypatch, rec)
 
 
 def test_arith_wrapper_passes_what_the_abi_takes(fake, L):

@@ -4,7 +4,7 @@ import os
 
 import pytest
 
-from support import ROOT, L, declared  # noqa: F401  (L: a fixture)
+from support import CSRC, INCLUDE, ROOT, L, declared  # noqa: F401  (L: a fixture)
 
 
 def header_symbols():
@@ -12,9 +12,30 @@ def header_symbols():
 
 
 def test_header_declares_what_python_binds():
-    from shared_simd_scan_amd._capi import SYMBOLS
+    from shared_simd_scan_amd._capi import HEADERS
 
-    assert sorted(s[0] for s in SYMBOLS) == header_symbols()
+    assert sorted(s[0] for s in HEADERS["mi355_scan.h"]) == header_symbols()
+
+
+def test_every_public_header_is_bound():
+    """the C headers under include/ are exactly the keys of _capi.HEADERS: a header nobody binds, or a list without its header,
+    fails here"""
+    import glob
+
+    from shared_simd_scan_amd._capi import HEADERS
+
+    assert {os.path.basename(p) for p in glob.glob(os.path.join(INCLUDE, "mi355_*.h"))} == set(HEADERS)
+
+
+def test_every_hip_source_is_compiled():
+    """every *.hip under csrc/ is the source of a compile command of `make all` (dry run: nothing is built)"""
+    import glob
+    import subprocess
+
+    out = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], check=True, capture_output=True, text=True).stdout
+    compiled = {os.path.realpath(tok) for line in out.splitlines() if " -c " in line for tok in line.split() if tok.endswith(".hip")}
+    sources = {os.path.realpath(p) for p in glob.glob(os.path.join(CSRC, "**", "*.hip"), recursive=True)}
+    assert sources and not sources - compiled, sorted(sources - compiled)
 
 
 def test_library_exports_every_declared_symbol(L):

@@ -1,6 +1,6 @@
 """The rows a bitmap selects, as a packed column (include/mi355_compact.h, ScanEngine.compact / compact_column).
 
-CPU: the header is plain C99 and declares exactly what _capi.COMPACT_SYMBOLS binds and the library exports; it carries its
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports; it carries its
 graph-capture verdict; mi355_compact_kernel (pure arithmetic) answers for c = 1..32; compact and compact_column hand the C ABI
 what they should (through a recording stand-in for the library); without a device the entry point fails with a message; every
 __global__ under csrc/compact/ is named by the launch record of a GPU case of this file; no source there reads a switch bit; the
@@ -17,13 +17,12 @@ ceil(n / 8) of the bitmap.  A tile is R = 2048 rows, a chunk K = 16384 rows (one
 import ctypes as C
 import functools
 import os
-import types
 
 import numpy as np
 import pytest
 
 import support
-from support import L, RecordingLib, eng, hostile_pack, plain_pack, record  # noqa: F401  (L, eng: fixtures)
+from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
 
 HEADER = "mi355_compact.h"
@@ -131,11 +130,7 @@ def test_compact_header_is_plain_c99():
 
 
 def test_compact_header_declares_what_python_binds(L):
-    from shared_simd_scan_amd import _capi
-
-    names, sigs = support.check_header_binds(
-        L, HEADER, _capi.COMPACT_SYMBOLS, ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h", "mi355_lookup.h"),
-        _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS + _capi.LOOKUP_SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert names == ["mi355_compact_dev", "mi355_compact_kernel"]
     sig = sigs["mi355_compact_dev"]
     assert sig[2] is C.c_uint64 and sig[3] is C.c_uint and sig[6] is C.c_uint64 and len(sig) == 8
@@ -158,17 +153,6 @@ def test_compact_kernel_answers_for_every_width(L):
     for bad in (0, 33, -1, 1 << 32):
         with pytest.raises(ValueError):
             compact_kernel(bad)
-
-
-@pytest.fixture
-def fake(monkeypatch, L):
-    """support.fake with the real buffer-size arithmetic, the new signatures, and a PackedColumn that takes any tensor"""
-    from shared_simd_scan_amd import _capi, engine
-
-    monkeypatch.setattr(engine, "PackedColumn", lambda data, n, c: types.SimpleNamespace(data=data, n=int(n), c=int(c)))
-    rec = RecordingLib(L)
-    rec._sig.update({name: args for name, _, args in _capi.COMPACT_SYMBOLS})
-    return support.fake_engine(monkeypatch, rec)
 
 
 def test_compact_wrapper_passes_what_the_abi_takes(fake, L, monkeypatch):

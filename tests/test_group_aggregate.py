@@ -1,7 +1,7 @@
 """Grouped aggregates over two packed columns (include/mi355_groupby.h, ScanEngine.group_aggregate): per value g of the key
 column the sum, count, min and max of the value column, optionally under a bitmap.
 
-CPU: the header is plain C99 and declares exactly what _capi.GROUP_SYMBOLS binds and the library exports; it carries its
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports; it carries its
 graph-capture verdict; group_aggregate hands the C ABI what it should (through a recording stand-in for the library, the idea
 of tests/test_scan_columns.py); without a device the entry point fails with a message; every __global__ under csrc/groupby/
 is named by the launch record of a GPU case of this file; no source there reads a switch bit; the data recipe is not vacuous.
@@ -105,9 +105,7 @@ def test_groupby_header_is_plain_c99():
 
 
 def test_groupby_header_declares_what_python_binds(L):
-    from shared_simd_scan_amd import _capi
-
-    names, sigs = support.check_header_binds(L, HEADER, _capi.GROUP_SYMBOLS, ("mi355_scan.h", "mi355_columns.h"), _capi.SYMBOLS + _capi.COLUMN_SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert names == ["mi355_group_aggregate_dev"]
     sig = sigs["mi355_group_aggregate_dev"]
     assert sig[2] is C.c_uint and sig[4] is C.c_uint and sig[5] is C.c_uint64 and len(sig) == 8

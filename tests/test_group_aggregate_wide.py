@@ -2,7 +2,7 @@
 dense domain [0, groups), groups <= 2^26, the sum, count, min and max of the value column, optionally under a bitmap; counted
 rows whose key is >= groups reach no group and are counted in `dropped`.
 
-CPU: the header is plain C99 and declares exactly what _capi.GROUP_WIDE_SYMBOLS binds and the library exports, no earlier header
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports, no earlier header
 or list knows the names; it carries its graph-capture verdict; group_aggregate_wide hands the C ABI what it should (through a
 recording stand-in for the library) and refuses a wrong `out` and differing row counts; without a device the entry point fails
 with a message; every __global__ under csrc/groupby_wide/ is named by the launch record of a GPU case of this file; no source
@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 
 import support
-from support import L, RecordingLib, eng, record, upload  # noqa: F401  (L, eng: fixtures)
+from support import L, eng, fake, record, upload  # noqa: F401  (L, eng, fake: fixtures)
 from test_kernel_paths import SENTINEL, Guarded, packbits
 
 HEADER = "mi355_groupby_wide.h"
@@ -198,12 +198,7 @@ def test_wide_header_is_plain_c99():
 
 
 def test_wide_header_declares_what_python_binds(L):
-    from shared_simd_scan_amd import _capi
-
-    names, sigs = support.check_header_binds(
-        L, HEADER, _capi.GROUP_WIDE_SYMBOLS,
-        ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h", "mi355_lookup.h", "mi355_compact.h", "mi355_arith.h"),
-        _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS + _capi.LOOKUP_SYMBOLS + _capi.COMPACT_SYMBOLS + _capi.ARITH_SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert names == ["mi355_group_aggregate_wide_dev", "mi355_group_wide_front_slots"]
     sig = sigs["mi355_group_aggregate_wide_dev"]
     assert sig[2] is C.c_uint and sig[4] is C.c_uint and sig[5] is C.c_uint64 and sig[7] is C.c_uint64 and len(sig) == 10
@@ -225,16 +220,6 @@ def test_wide_names_are_exported():
 
 def test_wide_header_carries_its_capture_verdict():
     support.check_capture_verdict(HEADER, r"no memset node", r"read at every replay")
-
-
-@pytest.fixture
-def fake(monkeypatch, L):
-    """support.fake with the new signatures (the idea of tests/test_arith.py)"""
-    from shared_simd_scan_amd import _capi
-
-    rec = RecordingLib(L)
-    rec._sig.update({name: args for name, _, args in _capi.GROUP_WIDE_SYMBOLS})
-    return support.fake_engine(monkeypatch, rec)
 
 
 def test_group_aggregate_wide_wrapper_passes_what_the_abi_takes(fake):

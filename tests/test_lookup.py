@@ -1,7 +1,7 @@
 """A packed column mapped through a device-resident packed table (include/mi355_lookup.h, ScanEngine.lookup):
 out[i] = table[v_i] if v_i < table_rows else miss, packed in and packed out.
 
-CPU: the header is plain C99 and declares exactly what _capi.LOOKUP_SYMBOLS binds and the library exports; it carries its
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports; it carries its
 graph-capture verdict; mi355_lookup_kernel (pure arithmetic) names the tier at every boundary; lookup hands the C ABI what it
 should (through a recording stand-in for the library); without a device the entry point fails with a message; every __global__
 under csrc/lookup/ is named by the launch record of a GPU case of this file; no source there reads a switch bit; the data
@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 import support
-from support import L, RecordingLib, eng, header_macro, hostile_pack, plain_pack, record  # noqa: F401  (L, eng: fixtures)
+from support import L, eng, fake, header_macro, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
 
 HEADER = "mi355_lookup.h"
@@ -160,10 +160,7 @@ def test_lookup_header_is_plain_c99():
 
 
 def test_lookup_header_declares_what_python_binds(L):
-    from shared_simd_scan_amd import _capi
-
-    names, sigs = support.check_header_binds(L, HEADER, _capi.LOOKUP_SYMBOLS, ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h"),
-                                             _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert names == ["mi355_lookup_dev", "mi355_lookup_kernel"]
     sig = sigs["mi355_lookup_dev"]
     assert sig[2] is C.c_uint64 and sig[3] is C.c_uint and sig[5] is C.c_uint64 and sig[6] is C.c_uint and sig[7] is C.c_uint32 and len(sig) == 9
@@ -223,15 +220,6 @@ def test_width_cases_reach_both_tiers(L):
     for case in WIDTH_CASES + TABLE_SIZE_CASES + SIZE_CASES + OFFSET_CASES + VIEW_CASES + LONG_CASES + CAPTURE_CASES:
         c, ct, T = case
         assert L.mi355_lookup_kernel(c, T, ct).decode() == want_family(c, ct, T), case
-
-
-# differs from support.fake: the buffer-size arithmetic goes to the real library, and lookup's result is a PackedColumn
-@pytest.fixture
-def fake(monkeypatch, L):
-    from shared_simd_scan_amd import engine
-
-    monkeypatch.setattr(engine, "PackedColumn", lambda data, n, c: types.SimpleNamespace(data=data, n=int(n), c=int(c)))  # (the real one wants a device tensor)
-    return support.fake_engine(monkeypatch, RecordingLib(L))
 
 
 def test_lookup_wrapper_passes_what_the_abi_takes(fake, L):

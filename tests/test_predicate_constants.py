@@ -54,7 +54,7 @@ def test_ctypes_masks_out_of_range_ints_without_error():
 
 def test_constant_arguments_have_the_c_types_the_helpers_target():
     """the helpers' ranges are chosen for these argument types (include/mi355_scan.h)"""
-    sig = {name: args for name, _, args in _capi.SYMBOLS}
+    sig = {name: args for name, _, args in _capi.HEADERS["mi355_scan.h"]}
     assert sig["mi355_scan_eq_dev"][4] is C.c_int32
     assert sig["mi355_scan_range_dev"][4:6] == [C.c_uint32, C.c_uint32]
     for name, idx in (("mi355_scan_where_dev", (5, 6)), ("mi355_scan_combine_dev", (5, 6)), ("mi355_scan_select_dev", (5, 6)),
@@ -141,7 +141,7 @@ class _RecordingLib:
 
     def __init__(self):
         self.calls = []
-        self._sig = {name: args for name, _, args in _capi.SYMBOLS}
+        self._sig = {name: args for name, _, args in _capi.HEADERS["mi355_scan.h"]}
 
     def __getattr__(self, name):
         argtypes = self._sig[name]

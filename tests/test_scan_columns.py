@@ -1,6 +1,6 @@
 """Scans that compare two packed columns row by row (include/mi355_columns.h, ScanEngine.scan_columns).
 
-CPU: the header is plain C99 and declares exactly what _capi.COLUMN_SYMBOLS binds and the library exports; engine.clamp_diff
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports; engine.clamp_diff
 keeps every comparison with a difference of two decoded values; scan_columns hands the C ABI what it should (through a
 recording stand-in for the library, the idea of tests/test_predicate_constants.py); without a device the entry point fails
 with a message.
@@ -68,9 +68,7 @@ def test_columns_header_is_plain_c99():
 
 
 def test_columns_header_declares_what_python_binds(L):
-    from shared_simd_scan_amd import _capi
-
-    names, sigs = support.check_header_binds(L, HEADER, _capi.COLUMN_SYMBOLS, ("mi355_scan.h",), _capi.SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert "mi355_scan_columns_dev" in names
 
 
@@ -81,7 +79,7 @@ def test_columns_header_carries_its_capture_verdict():
 def test_difference_constants_are_int64_arguments():
     from shared_simd_scan_amd import _capi
 
-    sig = {name: args for name, _, args in _capi.COLUMN_SYMBOLS}["mi355_scan_columns_dev"]
+    sig = {name: args for name, _, args in _capi.HEADERS[HEADER]}["mi355_scan_columns_dev"]
     assert sig[7] is C.c_int64 and sig[8] is C.c_int64
     assert sig[2] is C.c_uint and sig[4] is C.c_uint and sig[5] is C.c_uint64
 

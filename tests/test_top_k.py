@@ -1,6 +1,6 @@
 """The k largest or smallest rows of a packed column, as a bitmap (include/mi355_topk.h, ScanEngine.top_k / kth_value).
 
-CPU: the header is plain C99 and declares exactly what _capi.TOPK_SYMBOLS binds and the library exports; it carries its
+CPU: the header is plain C99 and declares exactly what _capi.HEADERS binds for it and the library exports; it carries its
 graph-capture verdict; mi355_top_k_passes (pure arithmetic) is 1 / 2 / 3 by width; top_k and kth_value hand the C ABI what they
 should (through a recording stand-in for the library); without a device the entry point fails with a message; every __global__
 under csrc/topk/ is named by the launch record of a GPU case of this file; no source there reads a switch bit; the data recipes
@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import support
-from support import L, RecordingLib, eng, hostile_pack, plain_pack, record  # noqa: F401  (L, eng: fixtures)
+from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 from test_compact import hostile_bitmap
 from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
 
@@ -219,19 +219,14 @@ def test_top_k_header_is_plain_c99():
 def test_top_k_header_declares_what_python_binds(L):
     from shared_simd_scan_amd import _capi
 
-    names, sigs = support.check_header_binds(
-        L, HEADER, _capi.TOPK_SYMBOLS,
-        ("mi355_scan.h", "mi355_columns.h", "mi355_groupby.h", "mi355_semijoin.h", "mi355_lookup.h", "mi355_compact.h", "mi355_arith.h",
-         "mi355_groupby_wide.h"),
-        _capi.SYMBOLS + _capi.COLUMN_SYMBOLS + _capi.GROUP_SYMBOLS + _capi.SEMIJOIN_SYMBOLS + _capi.LOOKUP_SYMBOLS + _capi.COMPACT_SYMBOLS
-        + _capi.ARITH_SYMBOLS + _capi.GROUP_WIDE_SYMBOLS)
+    names, sigs = support.check_header_binds(L, HEADER)
     assert names == ["mi355_top_k_dev", "mi355_top_k_passes"]
     sig = sigs["mi355_top_k_dev"]
     assert sig[2] is C.c_uint64 and sig[3] is C.c_uint and sig[5] is C.c_uint64 and sig[6] is C.c_int and len(sig) == 9
     assert sigs["mi355_top_k_passes"] == [C.c_uint] and L.mi355_top_k_passes.restype is C.c_uint
     text = support.header_text(HEADER)
     assert '#include "mi355_scan.h"' in text and text.count("#include") == 1
-    assert "mi355_topk.h" in _capi.__doc__
+    assert "mi355_topk.h" in _capi.HEADERS  # (the module's docstring points at HEADERS; it names no header of its own)
 
 
 def test_top_k_header_carries_its_capture_verdict():
@@ -249,15 +244,6 @@ def test_top_k_passes_by_width(L):
     for bad in (0, 33, -1, 1 << 32):
         with pytest.raises(ValueError):
             top_k_passes(bad)
-
-
-@pytest.fixture
-def fake(monkeypatch, L):
-    from shared_simd_scan_amd import _capi
-
-    rec = RecordingLib(L)
-    rec._sig.update({name: args for name, _, args in _capi.TOPK_SYMBOLS})
-    return support.fake_engine(monkeypatch, rec)
 
 
 def test_top_k_wrapper_passes_what_the_abi_takes(fake, monkeypatch):

@@ -129,6 +129,13 @@ HEADERS["mi355_topk.h"] = [
     ("mi355_top_k_passes", C.c_uint, [C.c_uint]),
 ]
 
+# the row ids of a column in value order
+HEADERS["mi355_sort.h"] = [
+    ("mi355_sort_rows_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _int, _u64, _vp, _vp, _u64, _vp]),
+    ("mi355_sort_rows_passes", C.c_uint, [C.c_uint]),
+    ("mi355_sort_rows_workspace_words", _u64, [_u64, _u64, C.c_uint]),
+]
+
 
 class Predicate(C.Structure):
     """mi355_predicate: one comparison `v OP a [, b]` of a shared where-scan"""

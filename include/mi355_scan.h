@@ -169,7 +169,9 @@ MI355_API int mi355_ctx_set_stream(mi355_ctx *ctx, void *hip_stream);
  * 0 / 2 = decoder / expander roles (default), 1 = the older single-role kernel, kept for A/B runs), "llc_resident_mib" (equality / range scans: MiB of the 256 MiB Infinity Cache
  * for the part of the column that is read with the default cache policy and so stays there for the next scan; -1 (default) a measured budget, applied
  * ONLY when the context's previous launch was a scan of the same column (pointer, n, c) into the same bitmap with the same mask, i.e. to back-to-back
- * identical buffers -- predicates written to different bitmaps, or a chain whose mask changes, never qualify; a scan captured into a graph keeps the
+ * identical buffers -- predicates written to different bitmaps, or a chain whose mask changes, never qualify, and a compute call of any kind
+ * between the two scans ends the repeat, one that launches nothing (n == 0, a refused call) included, while the memory helpers, mi355_ctx_synchronize,
+ * options and accessors do not (one place decides for every entry point: csrc/llc_repeat.hpp); a scan captured into a graph keeps the
  * decision made at capture time; 0 off; 1 .. 1024 an explicit budget for every call), "kernel_flags" (A/B switches of the kernels; results never depend on them except the two timing
  * ablations of the selection documented in DESIGN.md), "grid_cus" (0 = the device's CU count (default); 1 .. CU count: every
  * persistent grid is sized as if the device had that many CUs -- with "max_blocks_per_cu" = 1 and "grid_cus" = 1 a launch runs
@@ -458,7 +460,8 @@ MI355_API const char *mi355_shared_scan_kernel(mi355_ctx *ctx, unsigned c, unsig
  * The string stays valid until the calling thread calls this function again; NULL when ctx cannot be resolved. */
 MI355_API const char *mi355_ctx_last_launch(mi355_ctx *ctx);
 /* "llc_resident_mib": the divisor D the most recent launch ran with if it was an equality / range scan (0 nothing resident, 1 the whole
- * column, else every D-th 64 KiB granule), -1 otherwise.  Introspection for tests, like the launch record. */
+ * column, else every D-th 64 KiB granule), -1 otherwise -- whichever entry point launched since, or when a compute call since launched nothing
+ * (csrc/llc_repeat.hpp).  Introspection for tests, like the launch record. */
 MI355_API int mi355_ctx_last_llc_divisor(mi355_ctx *ctx);
 /* rows per wave tile of the scan kernels at width c (shard boundaries should be multiples of it) */
 MI355_API uint64_t mi355_tile_values(unsigned c);

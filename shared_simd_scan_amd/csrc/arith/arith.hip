@@ -93,7 +93,6 @@ int mi355_arith_dev(mi355_ctx *ctx, int op, const void *packed1_dev, unsigned c1
     r.k.miss = miss;
     r.k.nts = (uint32_t)one_pass_store_policy(out_bytes, ctx->scan_nt_stores);
     r.env = launch_env(ctx);
-    llc_forget(ctx);
     const hipError_t err = plan == kArithChecked ? launch_arith_checked(co, r) : launch_arith_exact(co, r);
     if (err != hipSuccess) return fail(MI355_E_HIP, "arith launch: %s", hipGetErrorString(err));
     return MI355_OK;

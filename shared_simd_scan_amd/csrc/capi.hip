@@ -53,23 +53,15 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
     r.shared_vpl = ctx->shared_vpl;
     r.scan_burst = ctx->scan_burst;
     r.llc_resident_mib = ctx->llc_resident_mib;
-    ctx->llc_last_d = -1;
-    r.llc_d_out = &ctx->llc_last_d;
-    if (r.op == kOpScanEq || r.op == kOpScanRange) {
-        // llc_prev is the launch that RUNS directly before this one.  Inside one capture that is the call captured before it
-        // (a graph replays its nodes in the order they were captured); a captured call has not run when the capture ends and
-        // the context never learns when its graph does, so across the boundary of a capture -- an eager call after a captured
-        // one, the first call of a capture, calls of two captures -- nothing is a repeat (llc_prev_capture: the capture's id, 0 = eager).
-        // (One host-side query of the stream's capture state per eq / range scan: no device work, no synchronisation.)
-        unsigned long long cap_id = 0;
-        const bool known = capture_state(ctx, &cap_id) != kCaptureUnknown; // unknown: neither a repeat nor something to repeat
-        r.llc_repeat = known && ctx->llc_prev[0] == r.scan.packed && ctx->llc_prev[1] == r.scan.out && ctx->llc_prev[2] == r.scan.and_mask &&
-                       ctx->llc_prev_n == r.scan.n && ctx->llc_prev_c == r.c && ctx->llc_prev_capture == cap_id;
-        ctx->llc_prev[0] = r.scan.packed, ctx->llc_prev[1] = r.scan.out, ctx->llc_prev[2] = r.scan.and_mask;
-        ctx->llc_prev_n = r.scan.n, ctx->llc_prev_c = r.c, ctx->llc_prev_capture = cap_id;
-        if (!known) ctx->llc_prev[0] = nullptr;
-    } else
-        ctx->llc_prev[0] = nullptr; // another kernel's traffic went through the cache
+    // eq / range: is it a repeat of the launch that runs directly before it (llc_repeat.hpp: the one place that decides, and the
+    // only launcher that asks).  One host-side query of the stream's capture state per such scan: no device work, no synchronisation.
+    const bool llc_scan = r.op == kOpScanEq || r.op == kOpScanRange;
+    const LlcScan llc{r.scan.packed, r.scan.out, r.scan.and_mask, r.scan.n, r.c};
+    unsigned long long cap_id = 0;
+    const bool cap_known = llc_scan && capture_state(ctx, &cap_id) != kCaptureUnknown;
+    int llc_d = -1;
+    r.llc_d_out = &llc_d;
+    r.llc_repeat = llc_scan && ctx->llc.is_repeat(llc, cap_known, cap_id, ctx->last_launch.size());
     r.scan.flags = kernel_switch_word(ctx->kernel_flags, r.op == kOpSelect); // (switches.hpp: the selection sees only its own)
     r.scan.scratch = ctx->kernel_scratch;
     if (r.max_blocks_per_cu == 0 && !ctx->tuned_bpc.empty()) {
@@ -82,6 +74,7 @@ int launch(mi355_ctx *ctx, LaunchReq &r)
     }
     hipError_t e = kGroups[(r.c - 1) / 4](r);
     if (e != hipSuccess) return fail(MI355_E_HIP, "kernel launch (op %d, c=%u): %s", r.op, r.c, hipGetErrorString(e));
+    if (llc_scan) ctx->llc.launched(llc, cap_known, cap_id, llc_d, ctx->last_launch.size());
     return MI355_OK;
 }
 
@@ -143,7 +136,6 @@ int launch_columns(mi355_ctx *ctx, ColumnsReq &r)
     r.k.s.scratch = ctx->kernel_scratch;
     // bitmap stores as scan2_kernel's: write-through below 768 MiB of bitmap, non-temporal beyond; "scan_nt_stores" overrides
     r.k.nts = (uint32_t)one_pass_store_policy(r.k.s.n / 8, ctx->scan_nt_stores);
-    llc_forget(ctx);
     hipError_t e = kColumnsGroups[(r.l.c - 1) / 4](r);
     if (e != hipSuccess) return fail(MI355_E_HIP, "kernel launch (column scan, c1=%u c2=%u): %s", r.l.c, r.k.c2, hipGetErrorString(e));
     return MI355_OK;
@@ -657,7 +649,7 @@ int mi355_ctx_last_llc_divisor(mi355_ctx *ctx)
 {
     Locked lk(ctx);
     if (lk.rc) return -1;
-    return ctx->llc_last_d;
+    return ctx->llc.last_divisor(ctx->last_launch.size());
 }
 
 const char *mi355_ctx_last_launch(mi355_ctx *ctx)

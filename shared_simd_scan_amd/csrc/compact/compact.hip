@@ -73,7 +73,6 @@ int mi355_compact_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsign
     r.k.c = c;
     r.k.nts = (uint32_t)one_pass_store_policy(packed_bytes(capacity < n ? capacity : n, c), ctx->scan_nt_stores);
     r.env = launch_env(ctx);
-    llc_forget(ctx);
     std::string *const rec = r.env.record;
     launch_rowid_prefix<true>(r.env, p, g);
     // also with capacity == 0: it leaves the total where the copy below takes it from

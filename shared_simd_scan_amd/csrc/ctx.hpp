@@ -1,9 +1,12 @@
 // ctx.hpp -- the context object behind include/mi355_scan.h and what every host-side translation unit of libmi355scan.so
 // shares (context.hip, which defines the helpers declared here, capi.hip, extras.hip, comm.hip and the feature units of the
 // Makefile's FEATURES table): error reporting, the entry prologue, the context's buffers.
+// MI355_ENTER and MI355_LAUNCH (dispatch.hpp) are all an entry point owes the context: the lock, the bound device, the launch record and,
+// through the record, the Infinity Cache's repeat state (llc_repeat.hpp), which no launcher but the eq / range path of capi.hip mentions.
 #pragma once
 
 #include "../../include/mi355_scan.h"
+#include "llc_repeat.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -32,13 +35,7 @@ struct mi355_ctx {
     std::map<uint32_t, int> tuned_bpc;
     int scan_burst = 0;  // 0: tiles per store burst by width; 1: one tile per burst
     int llc_resident_mib = -1; // eq / range scan: MiB of Infinity Cache for the part of the column read with the default policy; -1 auto, 0 off
-    // the buffers of the previous kernel launch if it was an eq / range scan (else null): auto keeps part of a column resident
-    // only when a scan repeats them, i.e. when what the cache holds is this column and this bitmap
-    const void *llc_prev[3] = {nullptr, nullptr, nullptr}; // column, bitmap, mask
-    int llc_last_d = -1;   // mi355_ctx_last_llc_divisor: ScanArgs::llc_d of the most recent launch, -1 if that was not an eq / range scan
-    uint64_t llc_prev_n = 0;
-    unsigned llc_prev_c = 0;
-    unsigned long long llc_prev_capture = 0; // id of the graph capture that launch was recorded into, 0 = it ran eagerly (capi.hip launch())
+    mi355::LlcRepeat llc; // is an eq / range scan a repeat (auto acts on repeats only), and mi355_ctx_last_llc_divisor: llc_repeat.hpp decides, from the launch record
     int dma_aux = 18; // bits 0-3: policy of the HBM->LDS loads (2 = non-temporal: the column is streamed once);
                       // bit 4: non-temporal stores in decompress
     // Every entry point that touches the state below holds `mu` while it does (the host-pointer flavours from their
@@ -113,7 +110,7 @@ struct Locked {
 
 // Entry, through MI355_ENTER(ctx) as an entry point's first line: Locked, then the outermost call on this context (the
 // host-pointer flavours, the compound calls and the sharded scans call other entry points with the lock held) starts a new launch
-// record and makes the context's device current.  Nested calls bind nothing: the outermost one did.  kKeepRecord: the memory
+// record (telling llc_repeat.hpp first what the call before left in it) and makes the context's device current.  Nested calls bind nothing: the outermost one did.  kKeepRecord: the memory
 // helpers and mi355_ctx_synchronize, which queue work on the context's stream but launch nothing -- the record of the last
 // compute call stays readable behind them.
 struct Entry : Locked {
@@ -124,7 +121,7 @@ struct Entry : Locked {
         const bool outermost = ctx->call_depth == 0;
         if (counted) ctx->call_depth++;
         if (!outermost) return;
-        if (counted) ctx->last_launch.clear();
+        if (counted) ctx->llc.call_begins(ctx->last_launch.size()), ctx->last_launch.clear(); // (did the call before end with an eq / range scan?)
         rc = bind(ctx);
     }
     ~Entry() { if (counted) ctx->call_depth--; }
@@ -163,8 +160,5 @@ struct LaunchEnv {
     std::string *record;                    // mi355_ctx_last_launch
 };
 inline LaunchEnv launch_env(mi355_ctx *ctx) { return {ctx->stream, ctx->device, grid_cus(ctx), ctx->max_blocks_per_cu, &ctx->last_launch}; }
-
-// another kernel's traffic went through the cache: the next eq / range scan is no repeat, and no divisor was chosen
-inline void llc_forget(mi355_ctx *ctx) { ctx->llc_prev[0] = nullptr, ctx->llc_last_d = -1; }
 
 } // namespace mi355

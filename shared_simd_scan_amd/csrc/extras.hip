@@ -21,6 +21,18 @@ unsigned capped_grid(mi355_ctx *ctx, uint64_t blocks, int per_cu, bool at_least_
     if (at_least_one && blocks == 0) blocks = 1;
     return (unsigned)(blocks < cap ? blocks : cap);
 }
+
+// pack_tiled_kernel by width: values per output dword, at most floor(31/c) + 2; one block per 8192-value tile, 4 resident per CU
+template <int SRC> void launch_pack_tiled(mi355_ctx *ctx, unsigned c, const PackArgs &a)
+{
+    const dim3 grid(capped_grid(ctx, (a.n + kPackTile - 1) / kPackTile, 4, true));
+    std::string *const rec = &ctx->last_launch;
+    if (c >= 16) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 3>), grid, dim3(256), 0, ctx->stream, a);
+    else if (c >= 8) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 5>), grid, dim3(256), 0, ctx->stream, a);
+    else if (c >= 4) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 9>), grid, dim3(256), 0, ctx->stream, a);
+    else if (c >= 2) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 17>), grid, dim3(256), 0, ctx->stream, a);
+    else MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 32>), grid, dim3(256), 0, ctx->stream, a);
+}
 } // namespace
 
 extern "C" {
@@ -44,18 +56,8 @@ static int pack_launch(mi355_ctx *ctx, int src, const void *values_dev, uint64_t
     const unsigned grid = capped_grid(ctx, (a.out_dwords + 255) / 256, 8, true);
     std::string *const rec = &ctx->last_launch;
     switch (src) {
-#define PACK_BY_WIDTH(SRC)                                                                                          \
-    do { /* values per output dword: at most floor(31/c) + 2; one block per 8192-value tile, 4 resident per CU */  \
-        const unsigned tgrid = capped_grid(ctx, (n + kPackTile - 1) / kPackTile, 4, true);                         \
-        if (c >= 16) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 3>), dim3(tgrid), dim3(256), 0, ctx->stream, a);    \
-        else if (c >= 8) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 5>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
-        else if (c >= 4) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 9>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
-        else if (c >= 2) MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 17>), dim3(tgrid), dim3(256), 0, ctx->stream, a); \
-        else MI355_LAUNCH(rec, 0, (pack_tiled_kernel<SRC, 32>), dim3(tgrid), dim3(256), 0, ctx->stream, a);           \
-    } while (0)
-    case kSrcU16: PACK_BY_WIDTH(kSrcU16); break;
-    case kSrcU32: PACK_BY_WIDTH(kSrcU32); break;
-#undef PACK_BY_WIDTH
+    case kSrcU16: launch_pack_tiled<kSrcU16>(ctx, c, a); break;
+    case kSrcU32: launch_pack_tiled<kSrcU32>(ctx, c, a); break;
     case kSrcMod: MI355_LAUNCH(rec, 0, pack_kernel<kSrcMod>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
     case kSrcSplitmix: MI355_LAUNCH(rec, 0, pack_kernel<kSrcSplitmix>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
     case kSrcIndex: MI355_LAUNCH(rec, 0, pack_kernel<kSrcIndex>, dim3(grid), dim3(256), 0, ctx->stream, a); break;
@@ -240,7 +242,7 @@ int mi355_aggregate_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     a.out = (unsigned long long *)out_dev;
     if (n == 0) {
         MI355_LAUNCH(&ctx->last_launch, 0, aggregate_init_kernel, dim3(1), dim3(1), 0, ctx->stream, a.out);
-    } else if (!launch_aggregate_width(c, a, grid_cus(ctx), ctx->stream, &ctx->last_launch)) {
+    } else if (launch_aggregate_width(c, launch_env(ctx), a) != hipSuccess) {
         return fail(MI355_E_INVALID, "width %u", c);
     }
     HIP_TRY(hipGetLastError());
@@ -259,7 +261,7 @@ int mi355_histogram_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     a.n = n;
     a.mask = (const uint8_t *)mask_dev;
     a.out = (unsigned long long *)counts_dev;
-    if (!launch_histogram_width(c, a, grid_cus(ctx), ctx->stream, &ctx->last_launch)) return fail(MI355_E_INVALID, "width %u", c);
+    if (launch_histogram_width(c, launch_env(ctx), a) != hipSuccess) return fail(MI355_E_INVALID, "width %u", c);
     HIP_TRY(hipGetLastError());
     return MI355_OK;
 }

@@ -4,7 +4,7 @@
 // one of the profiled hot-path kernels; included by extras.hip only.
 #pragma once
 
-#include "../dispatch.hpp"
+#include "../launch_util.hpp"
 #include "../kernels.hpp"
 
 namespace mi355 {
@@ -42,25 +42,10 @@ __global__ __launch_bounds__(kBlockThreads) void aggregate_kernel(AggArgs a)
     uint64_t tile = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
     const uint64_t nbytes = (a.n + 7) / 8;
 
-    // the lane's mask words of a tile (ragged end: only the bytes the bitmap is guaranteed to hold)
-    auto load_mask = [&](uint64_t t, uint32_t (&m)[WORDS]) {
+    auto load_mask = [&](uint64_t t, uint32_t (&m)[WORDS]) { // the lane's mask words of a tile; no mask: every row counts
 #pragma unroll
         for (int j = 0; j < WORDS; j++) m[j] = 0xffffffffu;
-        if (!a.mask) return;
-        const uint64_t at = t * G::BITMAP_BYTES + (uint64_t)lane * (WORDS * 4);
-        if (t < tc.nfull) {
-#pragma unroll
-            for (int j = 0; j < WORDS; j++) m[j] = ((const uint32_t *)(a.mask + at))[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < WORDS; j++) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++)
-                    if (at + 4 * j + b < nbytes) v |= (uint32_t)a.mask[at + 4 * j + b] << (8 * b);
-                m[j] = v;
-            }
-        }
+        if (a.mask) tc.template load_bitmap_words<true>(a.mask, t, lane, m, nbytes);
     };
 
     unsigned long long sum = 0, cnt = 0;
@@ -84,7 +69,7 @@ __global__ __launch_bounds__(kBlockThreads) void aggregate_kernel(AggArgs a)
             load_mask(next, mnext);
         }
         if (tile >= tc.nfull) { // rows behind the column count for nothing
-            const int64_t left = (int64_t)(a.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL;
+            const int64_t left = (int64_t)(a.n - tile * G::TILE_VALUES) - (int64_t)lane * VPL; // (lane_valid_rows compiles to another stream)
             const int valid = left >= VPL ? VPL : (left <= 0 ? 0 : (int)left);
 #pragma unroll
             for (int j = 0; j < WORDS; j++) m[j] &= tail_mask(valid, j);
@@ -147,30 +132,21 @@ __global__ __launch_bounds__(kBlockThreads) void aggregate_kernel(AggArgs a)
     }
 }
 
-template <int C> inline void launch_aggregate(const AggArgs &a, int num_cus, hipStream_t stream, std::string *rec)
+// Env: LaunchEnv (ctx.hpp).  Option "max_blocks_per_cu" does not reach these grids.
+template <int C, typename Env> inline void launch_aggregate(const Env &env, const AggArgs &a)
 {
     constexpr int VPL = scan_vpl(C, kModeEq);
     using G = ScanGeom<C, VPL>;
     const uint64_t ntiles = (a.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
     // one 4-wave block per CU keeps ~36-48 KiB of DMA in flight at c = 9, as the scans do; small tiles take two
-    const uint64_t blocks_wanted = (uint64_t)num_cus * (G::TILE_BYTES < 6144 ? 2 : 1);
-    const uint64_t blocks_needed = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned grid = (unsigned)(blocks_needed < blocks_wanted ? (blocks_needed ? blocks_needed : 1) : blocks_wanted);
-    MI355_LAUNCH(rec, 0, aggregate_init_kernel, dim3(1), dim3(1), 0, stream, a.out);
-    MI355_LAUNCH(rec, 0, (aggregate_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const unsigned grid = grid_for(ntiles, G::TILE_BYTES < 6144 ? 2 : 1, env.num_cus);
+    MI355_LAUNCH(env.record, 0, aggregate_init_kernel, dim3(1), dim3(1), 0, env.stream, a.out);
+    MI355_LAUNCH(env.record, 0, (aggregate_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, env.stream, a);
 }
 
-inline bool launch_aggregate_width(unsigned c, const AggArgs &a, int num_cus, hipStream_t stream, std::string *rec)
+template <typename Env> inline hipError_t launch_aggregate_width(unsigned c, const Env &env, const AggArgs &a)
 {
-    switch (c) {
-#define MI355_AGG_CASE(W) case W: launch_aggregate<W>(a, num_cus, stream, rec); return true;
-        MI355_AGG_CASE(1) MI355_AGG_CASE(2) MI355_AGG_CASE(3) MI355_AGG_CASE(4) MI355_AGG_CASE(5) MI355_AGG_CASE(6) MI355_AGG_CASE(7) MI355_AGG_CASE(8)
-        MI355_AGG_CASE(9) MI355_AGG_CASE(10) MI355_AGG_CASE(11) MI355_AGG_CASE(12) MI355_AGG_CASE(13) MI355_AGG_CASE(14) MI355_AGG_CASE(15) MI355_AGG_CASE(16)
-        MI355_AGG_CASE(17) MI355_AGG_CASE(18) MI355_AGG_CASE(19) MI355_AGG_CASE(20) MI355_AGG_CASE(21) MI355_AGG_CASE(22) MI355_AGG_CASE(23) MI355_AGG_CASE(24)
-        MI355_AGG_CASE(25) MI355_AGG_CASE(26) MI355_AGG_CASE(27) MI355_AGG_CASE(28) MI355_AGG_CASE(29) MI355_AGG_CASE(30) MI355_AGG_CASE(31) MI355_AGG_CASE(32)
-#undef MI355_AGG_CASE
-    default: return false;
-    }
+    return launch_by_width<1, 32>(c, a, [&](auto w, const AggArgs &q) { return launch_aggregate<decltype(w)::value>(env, q), hipSuccess; });
 }
 
 } // namespace mi355

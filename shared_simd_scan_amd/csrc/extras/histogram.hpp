@@ -4,7 +4,7 @@
 // counter and block at the end.  Built from the scan's tile pipeline; included by extras.hip only.
 #pragma once
 
-#include "../dispatch.hpp"
+#include "../launch_util.hpp"
 #include "../kernels.hpp"
 #include "../kernels/rt_column.hpp" // lane_valid_rows: the ragged last tile
 
@@ -37,24 +37,10 @@ __global__ __launch_bounds__(kBlockThreads) void histogram_kernel(HistArgs a)
     uint64_t tile = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
     const uint64_t nbytes = (a.n + 7) / 8;
 
-    auto load_mask = [&](uint64_t t, uint32_t (&m)[WORDS]) {
+    auto load_mask = [&](uint64_t t, uint32_t (&m)[WORDS]) { // the lane's mask words of a tile; no mask: every row counts
 #pragma unroll
         for (int j = 0; j < WORDS; j++) m[j] = 0xffffffffu;
-        if (!a.mask) return;
-        const uint64_t at = t * G::BITMAP_BYTES + (uint64_t)lane * (WORDS * 4);
-        if (t < tc.nfull) {
-#pragma unroll
-            for (int j = 0; j < WORDS; j++) m[j] = ((const uint32_t *)(a.mask + at))[j];
-        } else { // ragged end: only the bytes the bitmap is guaranteed to hold
-#pragma unroll
-            for (int j = 0; j < WORDS; j++) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++)
-                    if (at + 4 * j + b < nbytes) v |= (uint32_t)a.mask[at + 4 * j + b] << (8 * b);
-                m[j] = v;
-            }
-        }
+        if (a.mask) tc.template load_bitmap_words<true>(a.mask, t, lane, m, nbytes);
     };
 
     uint32_t mnext[WORDS];
@@ -101,28 +87,19 @@ __global__ __launch_bounds__(kBlockThreads) void histogram_kernel(HistArgs a)
     }
 }
 
-template <int C> inline void launch_histogram(const HistArgs &a, int num_cus, hipStream_t stream, std::string *rec)
+// Env: LaunchEnv (ctx.hpp).  Option "max_blocks_per_cu" does not reach this grid.
+template <int C, typename Env> inline void launch_histogram(const Env &env, const HistArgs &a)
 {
     constexpr int VPL = 128;
     using G = ScanGeom<C, VPL>;
     const uint64_t ntiles = (a.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
-    // two blocks per CU while tiles + counters of two blocks fit in the CU's 160 KiB (the LDS atomics want the second wave per SIMD)
-    const bool two = 2 * (4 * (size_t)G::LDS_BYTES + (4u << C)) + 1024 <= kCuLdsBytes;
-    const uint64_t blocks_wanted = (uint64_t)num_cus * (two ? 2 : 1);
-    const uint64_t blocks_needed = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const unsigned grid = (unsigned)(blocks_needed < blocks_wanted ? (blocks_needed ? blocks_needed : 1) : blocks_wanted);
-    MI355_LAUNCH(rec, 0, (histogram_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const unsigned grid = grid_for(ntiles, counters_bpc(G::LDS_BYTES, 4u << C), env.num_cus);
+    MI355_LAUNCH(env.record, 0, (histogram_kernel<C, VPL>), dim3(grid), dim3(kBlockThreads), 0, env.stream, a);
 }
 
-inline bool launch_histogram_width(unsigned c, const HistArgs &a, int num_cus, hipStream_t stream, std::string *rec)
+template <typename Env> inline hipError_t launch_histogram_width(unsigned c, const Env &env, const HistArgs &a)
 {
-    switch (c) {
-#define MI355_HIST_CASE(W) case W: launch_histogram<W>(a, num_cus, stream, rec); return true;
-        MI355_HIST_CASE(1) MI355_HIST_CASE(2) MI355_HIST_CASE(3) MI355_HIST_CASE(4) MI355_HIST_CASE(5) MI355_HIST_CASE(6) MI355_HIST_CASE(7)
-        MI355_HIST_CASE(8) MI355_HIST_CASE(9) MI355_HIST_CASE(10) MI355_HIST_CASE(11) MI355_HIST_CASE(12) MI355_HIST_CASE(13) MI355_HIST_CASE(14)
-#undef MI355_HIST_CASE
-    default: return false;
-    }
+    return launch_by_width<1, kHistogramMaxBits>(c, a, [&](auto w, const HistArgs &q) { return launch_histogram<decltype(w)::value>(env, q), hipSuccess; });
 }
 
 } // namespace mi355

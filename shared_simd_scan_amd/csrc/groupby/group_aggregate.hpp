@@ -132,6 +132,7 @@ template <int CK> __global__ __launch_bounds__(kBlockThreads, 2) void group_aggr
     };
     // the lane's mask word of tile t (ragged end: only the bytes the bitmap is guaranteed to hold)
     auto load_mask = [&](uint64_t t) -> uint32_t {
+        // (the kernel's own copy of bitmap_word_at's rule: with the shared form all twelve widths compile to another stream, c = 1 to 122 VGPRs for 116)
         if (!a.mask) return 0xffffffffu;
         const uint64_t at = t * G::BITMAP_BYTES + (uint64_t)lane * 4;
         if (t < tc.nfull) return *(const uint32_t *)(a.mask + at);

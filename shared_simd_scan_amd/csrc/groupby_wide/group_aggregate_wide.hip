@@ -74,7 +74,6 @@ int mi355_group_aggregate_wide_dev(mi355_ctx *ctx, const void *keys_dev, unsigne
     k.cv = cv;
     k.slots = group_wide_front_slots(ck, cv);
     const LaunchEnv env = launch_env(ctx);
-    llc_forget(ctx);
     launch_init(env, k);
     if (n) {
         const uint64_t ntiles = rt_ntiles(n);

@@ -224,6 +224,7 @@ static __global__ __launch_bounds__(kBlockThreads) void group_aggregate_wide_ker
     };
     // the lane's mask word of tile t (ragged end: only the bytes the bitmap is guaranteed to hold)
     auto load_mask = [&](uint64_t t) -> uint32_t {
+        // (the kernel's own copy of bitmap_word_at's rule: the shared form compiles to another stream)
         if (!a.mask) return 0xffffffffu;
         const uint64_t at = t * MASK_TILE + (uint64_t)lane * 4;
         if (t < nfull) return *(const uint32_t *)(a.mask + at);

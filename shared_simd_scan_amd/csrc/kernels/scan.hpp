@@ -42,6 +42,30 @@ template <int C, int VPL> struct TileCtx {
         else
             dma_tile_partial<G::TILE_BYTES, AUX>(src, data_bytes - t * G::TILE_BYTES, lds_wave, lane);
     }
+    // the lane's words of tile t of a bitmap over the column's rows (a mask, or an output read back): the whole dwords of a full
+    // tile, of the ragged one only the bytes the bitmap is guaranteed to hold, ceil(n / 8) -- nothing behind a caller's bitmap is read
+    // HAVE_NBYTES: the caller has ceil(n / 8) from its start and passes it (aggregate_kernel, histogram_kernel); the others (topk/)
+    // leave it to the ragged tile.  Either kind compiles to other scalar code with the other's form.
+    template <bool HAVE_NBYTES = false>
+    __device__ __forceinline__ void load_bitmap_words(const uint8_t *bits, uint64_t t, int lane, uint32_t (&m)[VPL / 32], uint64_t have_nbytes = 0) const
+    {
+        constexpr int WORDS = G::WORDS;
+        const uint64_t at = t * G::BITMAP_BYTES + (uint64_t)lane * (WORDS * 4);
+        if (t < nfull) {
+#pragma unroll
+            for (int j = 0; j < WORDS; j++) m[j] = ((const uint32_t *)(bits + at))[j];
+        } else {
+            const uint64_t nbytes = HAVE_NBYTES ? have_nbytes : (n + 7) / 8;
+#pragma unroll
+            for (int j = 0; j < WORDS; j++) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++)
+                    if (at + 4 * j + b < nbytes) v |= (uint32_t)bits[at + 4 * j + b] << (8 * b);
+                m[j] = v;
+            }
+        }
+    }
     // tail tile: zero bits >= n, write exactly ceil(n/8) bytes of the tile's bitmap; returns the lane's hit count
     __device__ __forceinline__ uint32_t finish_tail(uint64_t t, uint32_t (&v)[VPL / 32], uint8_t *dst, uint64_t byte_stride, int lane,
                                                     bool store = true) const

@@ -53,6 +53,13 @@ template <auto Kernel> int table_bpc(size_t lds, size_t fixed_lds, int device)
 // option "max_blocks_per_cu" (0 = no cap) on top of what a kernel admits
 inline int cap_bpc(int bpc, int max_blocks_per_cu) { return (max_blocks_per_cu > 0 && max_blocks_per_cu < bpc) ? max_blocks_per_cu : bpc; }
 
+// Blocks per CU of a kernel that counts into LDS next to its block's tiles (histogram_kernel, topk_hist_kernel): two while the tiles
+// (`tile_lds` bytes per wave) and the `counter_bytes` of two blocks fit in the CU's LDS -- the LDS atomics want the second wave per SIMD
+constexpr int counters_bpc(size_t tile_lds, size_t counter_bytes)
+{
+    return 2 * (kWavesPerBlock * tile_lds + counter_bytes) + 1024 <= (size_t)kCuLdsBytes ? 2 : 1;
+}
+
 // Blocks per CU the streaming scans want (the launcher takes the smaller of this and what the occupancy query admits).
 // Measured on MI355X (tools/sweep.py, 1e9 rows): the scans run fastest with ~36-48 KiB of LDS-DMA in flight per CU -- one
 // 4-wave block at c=9 (4 x 9 KiB tiles) -- and lose 3-6 % at the occupancy limit (more concurrent streams, same bytes).

@@ -78,7 +78,6 @@ int mi355_lookup_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigne
     r.k.miss = miss;
     r.k.nts = (uint32_t)one_pass_store_policy(out_bytes, ctx->scan_nt_stores);
     r.env = launch_env(ctx);
-    llc_forget(ctx);
     const hipError_t err = launch_by_width<1, 32>(ct, r, [](auto w, const LookupLaunch &q) { return launch_lookup<decltype(w)::value>(q); });
     if (err != hipSuccess) return fail(MI355_E_HIP, "lookup launch: %s", hipGetErrorString(err));
     return MI355_OK;

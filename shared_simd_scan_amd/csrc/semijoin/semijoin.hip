@@ -90,7 +90,6 @@ int mi355_semijoin_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsig
     r.in_lds = semijoin_in_lds(c, set_bits);
     r.store_policy = one_pass_store_policy(n / 8, ctx->scan_nt_stores);
     r.env = launch_env(ctx);
-    llc_forget(ctx);
     const hipError_t err = launch_by_width<1, 32>(c, r, [](auto w, const SemiLaunch &q) { return launch_semijoin<decltype(w)::value>(q); });
     if (err != hipSuccess) return fail(MI355_E_HIP, "semijoin launch: %s", hipGetErrorString(err));
     return MI355_OK;

@@ -104,7 +104,6 @@ int mi355_sort_rows_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsi
     k.c = c;
     k.flip = descending ? rt_vmask(c) : 0u;
     const LaunchEnv env = launch_env(ctx);
-    llc_forget(ctx);
     std::string *const rec = env.record;
     const unsigned passes = sort_passes(c);
     const unsigned item_grid = grid_for(sort_spans(plan.most), cap_bpc(8, env.max_blocks_per_cu), env.num_cus);

@@ -29,10 +29,7 @@ template <int C> hipError_t launch_top_k(const TopkLaunch &r)
     using G = ScanGeom<C, VPL>;
     std::string *const rec = r.env.record;
     const uint64_t ntiles = (r.k.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
-    // the histogram: two blocks per CU while the tiles and counters of two fit in the CU's LDS (the LDS atomics want the second
-    // wave per SIMD: launch_histogram's rule)
-    const bool two = 2 * (kWavesPerBlock * (size_t)G::LDS_BYTES + 4u * kTopkBuckets) + 1024 <= (size_t)kCuLdsBytes;
-    const unsigned hist_grid = grid_for(ntiles, cap_bpc(two ? 2 : 1, r.env.max_blocks_per_cu), r.env.num_cus);
+    const unsigned hist_grid = grid_for(ntiles, cap_bpc(counters_bpc(G::LDS_BYTES, 4u * kTopkBuckets), r.env.max_blocks_per_cu), r.env.num_cus);
     const unsigned emit_grid = grid_for(ntiles, scan_want_bpc(G::TILE_BYTES, r.env.max_blocks_per_cu), r.env.num_cus);
     const unsigned trim_grid = grid_for(r.k.nchunks, cap_bpc(2, r.env.max_blocks_per_cu), r.env.num_cus);
     const uint32_t vmask = C == 32 ? 0xffffffffu : ((1u << (C & 31)) - 1u);
@@ -113,7 +110,6 @@ int mi355_top_k_dev(mi355_ctx *ctx, const void *packed_dev, uint64_t n, unsigned
     r.plan = plan;
     r.passes = passes;
     r.env = launch_env(ctx);
-    llc_forget(ctx);
     HIP_TRY(hipMemsetAsync(ws, 0, words * sizeof(unsigned long long), ctx->stream));
     const hipError_t err = launch_by_width<1, 32>(c, r, [](auto w, const TopkLaunch &q) { return launch_top_k<decltype(w)::value>(q); });
     if (err != hipSuccess) return fail(MI355_E_HIP, "top_k launch: %s", hipGetErrorString(err));

@@ -96,29 +96,6 @@ struct TopkPickArgs {
 
 template <int C> constexpr int topk_vpl() { return scan_vpl(C, kModeEq); }
 
-// the lane's mask words of tile t: the whole dwords of a full tile, only the bytes the bitmap is guaranteed to hold of the ragged one
-template <int C, int VPL>
-__device__ __forceinline__ void topk_load_words(const uint8_t *bits, const TileCtx<C, VPL> &tc, uint64_t t, int lane, uint32_t (&m)[VPL / 32])
-{
-    using G = ScanGeom<C, VPL>;
-    constexpr int WORDS = G::WORDS;
-    const uint64_t at = t * G::BITMAP_BYTES + (uint64_t)lane * (WORDS * 4);
-    if (t < tc.nfull) {
-#pragma unroll
-        for (int j = 0; j < WORDS; j++) m[j] = ((const uint32_t *)(bits + at))[j];
-    } else {
-        const uint64_t nbytes = (tc.n + 7) / 8;
-#pragma unroll
-        for (int j = 0; j < WORDS; j++) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                if (at + 4 * j + b < nbytes) v |= (uint32_t)bits[at + 4 * j + b] << (8 * b);
-            m[j] = v;
-        }
-    }
-}
-
 // value K of the lane: one LDS atomic when its row qualifies and its higher digits are the prefix's
 template <int C, int VPL, bool MASKED, int K = 0>
 __device__ __forceinline__ void topk_count(const uint32_t (&w)[VPL * C / 32], const uint32_t (&m)[VPL / 32], uint32_t *hist, uint32_t flip,
@@ -168,7 +145,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_hist_kern
     uint64_t base = (uint64_t)blockIdx.x * kWavesPerBlock; // the block's first tile of this round: the same in all four waves
     if (base + wave < tc.ntiles) {
         tc.template issue<AUX>(a.packed, base + wave, lds_wave, lane);
-        if (a.mask) topk_load_words<C, VPL>(a.mask, tc, base + wave, lane, mnext);
+        if (a.mask) tc.load_bitmap_words(a.mask, base + wave, lane, mnext);
     }
     __syncthreads(); // the counters are zero
     uint32_t rounds = 0;
@@ -185,7 +162,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_hist_kern
             const uint64_t next = tile + stride;
             if (next < tc.ntiles) {
                 tc.template issue<AUX>(a.packed, next, lds_wave, lane);
-                if (a.mask) topk_load_words<C, VPL>(a.mask, tc, next, lane, mnext);
+                if (a.mask) tc.load_bitmap_words(a.mask, next, lane, mnext);
             }
             const bool full = tile < tc.nfull;
             if (!full) { // rows behind the column count for nothing
@@ -299,7 +276,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_emit_kern
     for (int j = 0; j < WORDS; j++) mnext[j] = 0xffffffffu;
     if (tile < tc.ntiles) {
         tc.template issue<AUX>(a.packed, tile, lds_wave, lane);
-        if (a.mask) topk_load_words<C, VPL>(a.mask, tc, tile, lane, mnext);
+        if (a.mask) tc.load_bitmap_words(a.mask, tile, lane, mnext);
     }
     while (tile < tc.ntiles) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the tile has landed, and the lane's mask words of it
@@ -312,7 +289,7 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_emit_kern
         const uint64_t next = tile + stride;
         if (next < tc.ntiles) {
             tc.template issue<AUX>(a.packed, next, lds_wave, lane);
-            if (a.mask) topk_load_words<C, VPL>(a.mask, tc, next, lane, mnext);
+            if (a.mask) tc.load_bitmap_words(a.mask, next, lane, mnext);
         }
         uint32_t ge[1][WORDS], eq[1][WORDS];
         decode_words<C, VPL, 0, 1, kModeRange, G::LANE_DWORDS>(w, ge, range_key);
@@ -371,12 +348,12 @@ template <int C> __global__ __launch_bounds__(kBlockThreads) void topk_trim_kern
             if (tile >= tc.ntiles) break;
             tc.template issue<0>(a.packed, tile, lds_wave, lane);
             uint32_t o[WORDS], q[WORDS]; // the output's words; where a tie may be: in the output, or (adding) among the qualifying rows
-            topk_load_words<C, VPL>(a.bitmap, tc, tile, lane, o);
+            tc.load_bitmap_words(a.bitmap, tile, lane, o);
             if (add) {
                 const int valid = lane_valid_rows<VPL>(tc.n, tile, lane);
 #pragma unroll
                 for (int j = 0; j < WORDS; j++) q[j] = 0xffffffffu;
-                if (a.mask) topk_load_words<C, VPL>(a.mask, tc, tile, lane, q);
+                if (a.mask) tc.load_bitmap_words(a.mask, tile, lane, q);
 #pragma unroll
                 for (int j = 0; j < WORDS; j++) q[j] &= tail_mask(valid, j);
             } else {

@@ -987,7 +987,7 @@ def test_replays_interleave_with_eager_calls(L, O):
 
 @gpu
 def test_llc_decision_is_frozen_at_capture(L):
-    """ctx->llc_prev after a captured call.  It describes the launch that RUNS directly before the next one.  Inside one capture
+    """The recorded scan (csrc/llc_repeat.hpp) after a captured call.  It describes the launch that RUNS directly before the next one.  Inside one capture
     that is the call captured before it -- a graph replays its nodes in capture order -- so the second of two identical captured
     scans is a repeat and gets the divisor an eager pair gets, frozen into the node.  A captured call has not run when its capture
     ends, and the context never learns when its graph does: across the boundary of a capture nothing is a repeat -- not the first

@@ -184,6 +184,21 @@ def test_auto_acts_on_repeats_only(L, O):
         assert L.mi355_ctx_last_llc_divisor(eng._ctx) == -1
         assert scan(1, 1) == 0
         assert scan(1, 1) == d
+        # ... whichever launcher it comes from: the where-scans' own, those of extras.hip, a feature unit's
+        small_bits = eng.alloc_bitmap(small.n).zero_()
+        others = {
+            "shared_scan_where": lambda: eng.shared_scan_where([("<", 5), (">", 100)], small),
+            "bitmap_count": lambda: eng.bitmap_count(small_bits, small.n),
+            "aggregate": lambda: eng.aggregate(small),
+            "histogram": lambda: eng.histogram(small),
+            "group_aggregate": lambda: eng.group_aggregate(small, small),
+            "generate": lambda: eng.generate("splitmix", small.n, c, 9),
+        }
+        for name, call in others.items():
+            call()
+            assert L.mi355_ctx_last_llc_divisor(eng._ctx) == -1, name
+            assert scan(1, 1) == 0, name
+            assert scan(1, 1) == d, name
         eng.set_option("llc_resident_mib", 0)
         assert scan(1, 1) == 0          # off
     finally:

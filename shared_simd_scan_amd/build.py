@@ -27,7 +27,7 @@ def kernel_sources_sha() -> str:
 
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hpp"))) + [os.path.join(CSRC, f) for f in
-                                                                           ("kernels.hpp", "dispatch.hpp", "launch_util.hpp", "shared_plan.hpp", "switches.hpp", "width_group.hip")]
+                                                                           ("kernels.hpp", "dispatch.hpp", "launch_util.hpp", "scan_plan.hpp", "shared_plan.hpp", "switches.hpp", "width_group.hip")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

@@ -12,6 +12,7 @@
 #include <typeinfo>
 
 #include "kernels.hpp"
+#include "scan_plan.hpp"
 
 namespace mi355 {
 
@@ -84,7 +85,7 @@ struct LaunchReq {
     int dma_aux;           // cache policy of the HBM->LDS loads: 0 default, 2 nt
     int scan_nt_stores;    // bitmap stores of the eq / range scan: -1 by size, 0 plain, 1 non-temporal
     int scan_burst;        // eq / range scan: 0 = tiles per store burst chosen by width (burst_k), 1 = one tile per burst
-    int llc_resident_mib;  // eq / range scan: Infinity Cache budget of the column's resident part, -1 auto, 0 off (width_group.hip llc_divisor)
+    int llc_resident_mib;  // eq / range scan: Infinity Cache budget of the column's resident part, -1 auto, 0 off (scan_plan.hpp llc_divisor)
     int llc_repeat;        // eq / range scan: the context's previous call was a scan of the same column into the same bitmap (auto acts on repeats only)
     int *llc_d_out;        // eq / range scan: non-null = where the launcher reports the divisor it chose (mi355_ctx_last_llc_divisor)
     int select_single;     // kOpSelect: 1 = the older single-role kernel (option "select_kernel" = 1, A/B), 0 = decoder / expander roles
@@ -104,14 +105,11 @@ inline std::string *record_of(const LaunchReq &r) { return r.record; }
 inline bool dry_run(std::string *) { return false; }
 inline bool dry_run(const LaunchReq &r) { return r.choice_out != nullptr; }
 
-// Persistent grid: at most (resident blocks per CU) x (CUs) blocks of 4 waves; each wave strides
-// over the wave tiles.  Small inputs get one wave per tile.
-inline unsigned grid_for(uint64_t ntiles, int blocks_per_cu, int num_cus)
+// the rules (scan_plan.hpp: grid_for, the store policies, the plans) read these fields
+static_assert(kPlanWavesPerBlock == kWavesPerBlock, "scan_plan.hpp repeats kWavesPerBlock");
+inline PlanReq plan_req(const LaunchReq &r)
 {
-    uint64_t want = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    uint64_t cap = (uint64_t)blocks_per_cu * (uint64_t)num_cus;
-    if (want < 1) want = 1;
-    return (unsigned)(want < cap ? want : cap);
+    return PlanReq{r.num_cus, r.max_blocks_per_cu, r.dma_aux, r.scan_nt_stores, r.scan_burst, r.llc_resident_mib, r.llc_repeat, r.select_single};
 }
 
 constexpr int kNumGroups = 8; // widths 1..32, 4 per group

@@ -1,13 +1,16 @@
 // launch_util.hpp -- the host-side launch helpers that the translation units with a launcher share, one copy of each: capi.hip,
 // extras.hip, the three group units (width_group.hip, predicates/where_group.hip, predicates/columns_group.hip) and the feature
 // units (groupby/group_aggregate.hip, groupby_wide/group_aggregate_wide.hip, semijoin/semijoin.hip, lookup/lookup.hip, compact/compact.hip,
-// arith/arith_kernels.hip, topk/top_k.hip).  No device code: kernels are only launched from here (launch_tier, launch_rowid_prefix).
+// arith/arith_kernels.hip, topk/top_k.hip, sort/sort_rows.hip; arith/arith.hip for the store policy).  No device code: kernels are only
+// launched from here (launch_tier, launch_rowid_prefix).  What needs HIP or a kernel lives here; the pure rules -- grid_for, cap_bpc,
+// scan_want_bpc, the store policies, the plans of the group units -- are in scan_plan.hpp, which dispatch.hpp includes.
 #pragma once
 
 #include <atomic>
 #include <type_traits>
 
 #include "dispatch.hpp"
+#include "scan_plan.hpp"
 
 namespace mi355 {
 
@@ -50,27 +53,11 @@ template <auto Kernel> int table_bpc(size_t lds, size_t fixed_lds, int device)
     return by_lds < 1 ? 1 : (by_lds < bpc ? by_lds : bpc);
 }
 
-// option "max_blocks_per_cu" (0 = no cap) on top of what a kernel admits
-inline int cap_bpc(int bpc, int max_blocks_per_cu) { return (max_blocks_per_cu > 0 && max_blocks_per_cu < bpc) ? max_blocks_per_cu : bpc; }
-
 // Blocks per CU of a kernel that counts into LDS next to its block's tiles (histogram_kernel, topk_hist_kernel): two while the tiles
 // (`tile_lds` bytes per wave) and the `counter_bytes` of two blocks fit in the CU's LDS -- the LDS atomics want the second wave per SIMD
 constexpr int counters_bpc(size_t tile_lds, size_t counter_bytes)
 {
     return 2 * (kWavesPerBlock * tile_lds + counter_bytes) + 1024 <= (size_t)kCuLdsBytes ? 2 : 1;
-}
-
-// Blocks per CU the streaming scans want (the launcher takes the smaller of this and what the occupancy query admits).
-// Measured on MI355X (tools/sweep.py, 1e9 rows): the scans run fastest with ~36-48 KiB of LDS-DMA in flight per CU -- one
-// 4-wave block at c=9 (4 x 9 KiB tiles) -- and lose 3-6 % at the occupancy limit (more concurrent streams, same bytes).
-// So: the number of blocks whose tiles add up to ~40 KiB, at least 1.
-inline int scan_want_bpc(int tile_bytes, int max_blocks_per_cu)
-{
-    if (max_blocks_per_cu > 0) return max_blocks_per_cu;
-    int want = (40 * 1024 + 2 * tile_bytes) / (kWavesPerBlock * tile_bytes); // rounded
-    if (want < 1) want = 1;
-    if (want > 4) want = 4; // c = 1, 2 (1-2 KiB tiles): four blocks per CU beat eight by 20 % / 6 % (launches back to back)
-    return want;
 }
 
 // One tier of a kernel with a table in LDS, launched on a persistent grid over `ntiles` wave tiles: `lds` bytes of dynamic LDS next
@@ -108,31 +95,6 @@ template <bool COUNT, typename Env> void launch_rowid_prefix(const Env &env, con
     MI355_LAUNCH(env.record, 0, rowid_scan_kernel, dim3((unsigned)p.ngroups), dim3(256), 0, env.stream, g);
 }
 
-// ---- store policies: `scan_nt_stores` is the option (-1 = by size), `out_bytes` what the launch writes ------------------
-
-// Kernels that write every output byte once, in one pass (the eq / range scans, in_kernel, scan2_kernel, the column scan,
-// the pair kernel and the one-pass LUT kernels): 0 plain, 1 non-temporal, 2 write-through (sc1).
-// Bitmap stores, measured with launches back to back (bench.py --store-policy, same box, 1e9 x 9 bit unless noted):
-// write-through (sc1) 0.201 ms, plain 0.207, non-temporal 0.216 -- dirty bitmap lines do not pile up in L2 to be
-// written back under the next launch's read stream; c = 21: 0.438 / 0.467 / 0.457; c = 5: 0.127 / 0.129 / 0.136.
-// Bitmaps far beyond the 256 MiB Infinity Cache prefer non-temporal stores: 4e9 rows sc1 0.82 ms / nt 0.85,
-// 8e9 rows (1 GB of bitmap) 1.74 / 1.72.
-// The one-pass shared scans follow (launches back to back, P = 8: 1e8 rows sc1 0.046 ms / plain 0.047 / nt 0.049; 1e9 rows
-// nt 0.353-0.383 / sc1 0.347-0.393 / plain 0.40).
-inline int one_pass_store_policy(uint64_t out_bytes, int scan_nt_stores)
-{
-    return scan_nt_stores < 0 ? (out_bytes > (768ull << 20) ? 1 : 2) : scan_nt_stores;
-}
-
-// The multi-pass shared scans of more than 8 keys / predicates: non-temporal result stores unless the P bitmaps together
-// are small.  Measured (tools/sweep.py --nts 0,1, P = 8, c = 9): 1e8 rows (100 MB of bitmaps) 0.0540 -> 0.0525 ms, 5e8
-// 0.220 -> 0.214, 1e9 0.409 -> 0.372; c = 17: -1..-4 %.  Unlike the single bitmap of the plain scans, these outputs gain
-// nothing from staying in the Infinity Cache.
-inline bool multi_pass_nt_stores(uint64_t out_bytes, int scan_nt_stores)
-{
-    return scan_nt_stores < 0 ? out_bytes > (64ull << 20) : scan_nt_stores != 0;
-}
-
 // ---- compile-time fan-out ------------------------------------------------------------------------------------------------
 
 // The width ladder of a group translation unit: f(std::integral_constant<int, C>{}, r) for the C in LO .. HI that c names.
@@ -164,6 +126,16 @@ template <int kMaxRc, bool kBigWidth, typename F> void with_rc_big(int rc, bool 
         if (rc == 2) return with_big(std::integral_constant<int, 2>{});
     }
     with_big(std::integral_constant<int, 0>{});
+}
+
+// A planned AUX word (scan_plan.hpp) as a template argument: f(std::integral_constant<int, aux>{}) for the one of kAux, kMore... that
+// `aux` names -- the forms a kernel is instantiated in, and no other; the plans give nothing else (the last stands for "none of the others")
+template <int kAux, int... kMore, typename F> void with_aux(int aux, F f)
+{
+    if constexpr (sizeof...(kMore) > 0) {
+        if (aux != kAux) return with_aux<kMore...>(aux, f);
+    }
+    f(std::integral_constant<int, kAux>{});
 }
 
 // what a launcher returns: in a dry run (LaunchReq::choice_out) nothing was launched, so nothing can have failed

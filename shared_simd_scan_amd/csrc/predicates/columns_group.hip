@@ -22,17 +22,12 @@ __global__ __launch_bounds__(kBlockThreads, (columns_occ<C1, VPL, SAME>())) void
 
 namespace {
 
-// Blocks per CU.  Both columns in registers: the plain scans' rule on the two tiles together (scan2_kernel: the DMA in
-// flight per CU is what counts, about 40 KiB), inside what LDS and registers admit.  Column 2 read from LDS (32 rows per
-// lane, small tiles, LDS reads all through the decode): as many blocks as fit, up to 4 waves per SIMD.
+// Blocks per CU: what the scan wants (scan_plan.hpp columns_want_bpc), inside what LDS and registers admit
 template <auto Kernel> int columns_bpc(const ColumnsReq &r, bool same, int tile_bytes, size_t lds)
 {
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, Kernel, kBlockThreads, lds) != hipSuccess || occ < 1) occ = 1;
-    int want = same ? (40 * 1024 + 2 * tile_bytes) / (kWavesPerBlock * tile_bytes) : 4;
-    if (r.l.max_blocks_per_cu > 0) want = r.l.max_blocks_per_cu;
-    if (want < 1) want = 1;
-    if (want > 4) want = 4;
+    const int want = columns_want_bpc(same, tile_bytes, r.l.max_blocks_per_cu);
     return want < occ ? want : occ;
 }
 

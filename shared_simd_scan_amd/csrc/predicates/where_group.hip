@@ -35,62 +35,75 @@ template <int C> int where_lut_bpc(const WhereReq &r, bool linear, size_t lds_pe
     return want < fit ? want : fit;
 }
 
-// one launch of a where-kernel: the dynamic-LDS limit (max_dyn > 0), then the launch (the kernels read no flag bits)
-template <auto Kernel> void launch_where_kernel(const WhereReq &r, dim3 grid, size_t dyn_lds = 0, int max_dyn = 0)
+// ---- which kernel a where-scan of P >= 2 predicates runs, decided once: a pure function of the request, as plan_shared() ------
+struct WherePlan {
+    int choice;     // WhereChoice, what mi355_shared_where_kernel names
+    int aux;        // the kernel's AUX: 2 plain, 18 non-temporal, 34 write-through result stores
+    size_t dyn_lds; // dynamic LDS bytes
+    int max_dyn;    // > 0: the most dynamic LDS the kernel is ever given
+    int want_bpc;   // blocks per CU; kWhereChain: the option's cap on what the occupancy query admits, 0 = none
+};
+
+template <int C> WherePlan plan_where(const WhereReq &r)
 {
-    if (max_dyn > 0) allow_dynamic_lds<Kernel>(max_dyn, r.l.device);
-    MI355_LAUNCH(r.l, 0, Kernel, grid, dim3(kBlockThreads), dyn_lds, r.l.stream, r.w);
+    if constexpr (C <= 16) {
+        using G = ScanGeom<C, kWhereVpl>;
+        const uint32_t P = r.w.s.nkeys;
+        const uint64_t out_bytes = (r.w.s.n / 8) * P; // the P bitmaps together
+        const bool linear = r.w.s.layout != 0;
+        if (P <= 8) {
+            // result stores as shared_lut_kernel's launcher: write-through below 768 MiB of output, non-temporal beyond (AUX as in_kernel's)
+            const size_t per_block = 4 * G::LDS_BYTES + WhereLutGeom<C>::TABLE_BYTES + (linear ? 4 * (kWhereVpl / 8) * 8 * 64 : 0) + 512;
+            return WherePlan{kWhereLut, in_aux(one_pass_store_policy(out_bytes, r.l.scan_nt_stores)), 0, 0, where_lut_bpc<C>(r, linear, per_block)};
+        }
+        if (where_tables_fit<C>(P)) {
+            // per-predicate result stores: non-temporal unless the P bitmaps together are small (the rule of the equality
+            // scans of more than 8 keys); linear rows: plain
+            const size_t dyn = where_table_bytes<C>(P);
+            return WherePlan{kWhereLutMulti, (!linear && multi_pass_nt_stores(out_bytes, r.l.scan_nt_stores)) ? 18 : 2, dyn,
+                             (int)(kCuLdsBytes - where_static_lds<C>()), where_lut_bpc<C>(r, linear, dyn + where_static_lds<C>())};
+        }
+    }
+    return WherePlan{kWhereChain, 2, 0, 0, r.l.max_blocks_per_cu > 0 ? r.l.max_blocks_per_cu : 0};
 }
 
+// one launch of a planned where-kernel: the dynamic-LDS limit, the grid, then the launch (the kernels read no flag bits)
+template <auto Kernel> void launch_where_kernel(const WhereReq &r, const WherePlan &p, int bpc)
+{
+    constexpr uint64_t tile_values = 64 * (uint64_t)kWhereVpl;
+    const uint64_t ntiles = (r.w.s.n + tile_values - 1) / tile_values;
+    if (p.max_dyn > 0) allow_dynamic_lds<Kernel>(p.max_dyn, r.l.device);
+    MI355_LAUNCH(r.l, 0, Kernel, dim3(grid_for(ntiles, bpc, r.l.num_cus)), dim3(kBlockThreads), p.dyn_lds, r.l.stream, r.w);
+}
+
+// launches what plan_where() decided.  The only place that names the where-kernels' templates.
 template <int C> hipError_t launch_where(const WhereReq &r)
 {
     constexpr int VPL = kWhereVpl;
-    using G = ScanGeom<C, VPL>;
-    const ScanArgs &s = r.w.s;
-    const uint32_t P = s.nkeys;
-    const bool linear = s.layout != 0;
-    const uint64_t ntiles = (s.n + G::TILE_VALUES - 1) / G::TILE_VALUES;
-    int choice = kWhereChain;
-    if constexpr (C <= 16) choice = P <= 8 ? kWhereLut : (where_tables_fit<C>(P) ? kWhereLutMulti : kWhereChain);
-    if (r.l.choice_out) *r.l.choice_out = choice; // introspection (mi355_shared_where_kernel): MI355_LAUNCH launches nothing
+    const WherePlan p = plan_where<C>(r);
+    const bool linear = r.w.s.layout != 0;
+    if (r.l.choice_out) *r.l.choice_out = p.choice; // introspection (mi355_shared_where_kernel): MI355_LAUNCH launches nothing
     if constexpr (C <= 16) {
-        if (choice == kWhereLut) {
-            // result stores as shared_lut_kernel's launcher: write-through below 768 MiB of output, non-temporal beyond
-            const int spol = one_pass_store_policy((s.n / 8) * P, r.l.scan_nt_stores); // 0 plain, 1 nt, 2 sc1
-            const size_t per_block = 4 * G::LDS_BYTES + WhereLutGeom<C>::TABLE_BYTES + (linear ? 4 * (VPL / 8) * 8 * 64 : 0) + 512;
-            const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, per_block), r.l.num_cus));
-            auto go = [&](auto layout) {
-                constexpr int LAYOUT = decltype(layout)::value;
-                if (spol == 1)
-                    launch_where_kernel<shared_where_lut_kernel<C, 18, VPL, LAYOUT, false>>(r, grid);
-                else if (spol == 2)
-                    launch_where_kernel<shared_where_lut_kernel<C, 34, VPL, LAYOUT, false>>(r, grid);
-                else
-                    launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, LAYOUT, false>>(r, grid);
-            };
-            linear ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 0>{});
+        if (p.choice == kWhereLut) {
+            with_aux<2, 18, 34>(p.aux, [&](auto aux) {
+                constexpr int AUX = decltype(aux)::value;
+                linear ? launch_where_kernel<shared_where_lut_kernel<C, AUX, VPL, 1, false>>(r, p, p.want_bpc)
+                       : launch_where_kernel<shared_where_lut_kernel<C, AUX, VPL, 0, false>>(r, p, p.want_bpc);
+            });
             return launch_status(r.l);
         }
         if constexpr (where_tables_fit<C>(9)) // (c = 16: two tables never fit, the multi-pass form is not instantiated)
-        if (choice == kWhereLutMulti) {
-            // per-predicate result stores: non-temporal unless the P bitmaps together are small (the rule of the equality
-            // scans of more than 8 keys)
-            const bool nt_stores = multi_pass_nt_stores((s.n / 8) * P, r.l.scan_nt_stores);
-            const size_t dyn = where_table_bytes<C>(P);
-            const int max_dyn = (int)(kCuLdsBytes - where_static_lds<C>());
-            const dim3 grid(grid_for(ntiles, where_lut_bpc<C>(r, linear, dyn + where_static_lds<C>()), r.l.num_cus));
+        if (p.choice == kWhereLutMulti) {
             if (linear)
-                launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, 1, true>>(r, grid, dyn, max_dyn);
-            else if (nt_stores)
-                launch_where_kernel<shared_where_lut_kernel<C, 18, VPL, 0, true>>(r, grid, dyn, max_dyn);
+                launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, 1, true>>(r, p, p.want_bpc);
             else
-                launch_where_kernel<shared_where_lut_kernel<C, 2, VPL, 0, true>>(r, grid, dyn, max_dyn);
+                with_aux<2, 18>(p.aux, [&](auto aux) { launch_where_kernel<shared_where_lut_kernel<C, decltype(aux)::value, VPL, 0, true>>(r, p, p.want_bpc); });
             return launch_status(r.l);
         }
     }
     if constexpr (C >= 11) { // (at c <= 10 every list fits the tables)
-        static const int bpc = blocks_per_cu(shared_where_chain_kernel<C, 2, VPL>);
-        launch_where_kernel<shared_where_chain_kernel<C, 2, VPL>>(r, dim3(grid_for(ntiles, cap_bpc(bpc, r.l.max_blocks_per_cu), r.l.num_cus)));
+        static const int occ = blocks_per_cu(shared_where_chain_kernel<C, 2, VPL>);
+        launch_where_kernel<shared_where_chain_kernel<C, 2, VPL>>(r, p, cap_bpc(occ, p.want_bpc));
         return launch_status(r.l);
     }
     return hipErrorInvalidValue;

@@ -5,8 +5,11 @@
 // to ask and fall back to one block per CU, so the grid column means nothing here.
 //
 // stdin, one case per line:  op c P layout hits n kernel_flags shared_vpl scan_nt_stores max_blocks_per_cu dma_aux scan_burst select_single
-//   (kernel_flags: the option as a caller sets it; it goes through kernel_switch_word() as in capi.hip's launch())
-// stdout, one line per case: <family or -1> TAB <launch record line>
+//   [llc_resident_mib llc_repeat]
+//   (kernel_flags: the option as a caller sets it; it goes through kernel_switch_word() as in capi.hip's launch(); without the two
+//   trailing columns the Infinity Cache option is auto and the call no repeat, so the divisor is 0)
+// stdout, one line per case: <family or -1> TAB <launch record line>; with the trailing columns also TAB <the Infinity Cache divisor
+//   the launcher chose (LaunchReq::llc_d_out), -1 = the op reports none>
 // --switches: the table of switches.hpp instead, one row per line: name TAB option value TAB kernel bit TAB receiver
 #include <cstdio>
 #include <cstring>
@@ -26,9 +29,13 @@ int main(int argc, char **argv)
     int op, layout, hits, shared_vpl, nts, max_bpc, dma_aux, burst, single;
     unsigned c, P, flags;
     unsigned long long n, dummy = 0;
-    while (scanf("%d %u %u %d %d %llu %u %d %d %d %d %d %d", &op, &c, &P, &layout, &hits, &n, &flags, &shared_vpl, &nts, &max_bpc, &dma_aux,
-                 &burst, &single) == 13) {
-        if (c < 1 || c > 32) return 2;
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        int llc_mib = -1, llc_repeat = 0, llc_d = -1;
+        const int fields = sscanf(line, "%d %u %u %d %d %llu %u %d %d %d %d %d %d %d %d", &op, &c, &P, &layout, &hits, &n, &flags, &shared_vpl, &nts,
+                                  &max_bpc, &dma_aux, &burst, &single, &llc_mib, &llc_repeat);
+        if (fields == EOF) continue; // a blank line
+        if ((fields != 13 && fields != 15) || c < 1 || c > 32) return 2;
         std::string record;
         int family = -1;
         LaunchReq r{};
@@ -39,7 +46,9 @@ int main(int argc, char **argv)
         r.dma_aux = dma_aux;
         r.scan_nt_stores = nts;
         r.scan_burst = burst;
-        r.llc_resident_mib = -1;
+        r.llc_resident_mib = llc_mib;
+        r.llc_repeat = llc_repeat;
+        r.llc_d_out = &llc_d;
         r.select_single = single;
         r.shared_vpl = shared_vpl;
         r.record = &record;
@@ -56,7 +65,10 @@ int main(int argc, char **argv)
             return 1;
         }
         if (!record.empty() && record.back() == '\n') record.pop_back();
-        printf("%d\t%s\n", family, record.c_str());
+        if (fields == 15)
+            printf("%d\t%s\t%d\n", family, record.c_str(), llc_d);
+        else
+            printf("%d\t%s\n", family, record.c_str());
     }
     return 0;
 }

@@ -24,7 +24,7 @@ MODES = ["eq", "range", "count", "mask"]
 
 
 def divisor(budget_mib, column_bytes, bitmap_bytes):
-    """width_group.hip llc_divisor() for an explicit budget (small bitmaps, nt column loads)"""
+    """scan_plan.hpp llc_divisor() for an explicit budget (small bitmaps, nt column loads)"""
     budget = budget_mib * MIB
     if budget_mib <= 0 or budget <= bitmap_bytes:
         return 0

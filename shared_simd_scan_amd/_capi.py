@@ -129,6 +129,14 @@ HEADERS["mi355_topk.h"] = [
     ("mi355_top_k_passes", C.c_uint, [C.c_uint]),
 ]
 
+# the set of a column's values as a bitmap over the value domain, the members' ranks as a packed table.  (In front of mi355_sort.h:
+# tests/test_sort_rows.py wants that header to stay the dict's last key.)
+HEADERS["mi355_distinct.h"] = [
+    ("mi355_value_set_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _vp, _u64, _int, _vp]),
+    ("mi355_value_set_kernel", C.c_char_p, [C.c_uint, _u64]),
+    ("mi355_set_ranks_dev", _int, [_vp, _vp, _u64, C.c_uint, _u32, _vp, _vp]),
+]
+
 # the row ids of a column in value order
 HEADERS["mi355_sort.h"] = [
     ("mi355_sort_rows_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _int, _u64, _vp, _vp, _u64, _vp]),

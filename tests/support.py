@@ -1,5 +1,7 @@
 """What the test files share: where things are, the library and engine fixtures, what a public header declares, a recording
-stand-in for the library, packed uploads, and the checks every feature header and feature source directory gets.
+stand-in for the library, launch records, guarded buffers, packed and hostile uploads, the runtime of the alignment tables, the
+rank-process helpers, and the checks every feature header and feature source directory gets.  capture.py (graph capture) and
+kernel_cases.py (the kernel-path case table) stand beside it; no test file imports from another test file.
 
 A plain module, not a conftest: a test file imports what it uses by name, fixtures included (pytest takes an imported fixture as
 the importing module's own, so the module-scoped ones still live once per test file).  A copy that differs from what is here
@@ -7,18 +9,22 @@ stays in its test file, with a comment that says how."""
 import ctypes as C
 import glob
 import os
+import queue
 import re
+import socket
 import subprocess
+import time
 import types
 
 import numpy as np
 import pytest
 
-from test_kernel_paths import parse_record
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
 CSRC = os.path.join(ROOT, "shared_simd_scan_amd", "csrc")
+
+E_INVALID = -1   # MI355_E_INVALID
+SENTINEL = 0xEE  # the fill of every guard byte and of every output in front of a call
 
 
 @pytest.fixture(scope="module")
@@ -147,7 +153,56 @@ def fake(monkeypatch, L):
     return fake_engine(monkeypatch, RecordingLib(L))
 
 
+# ---- launch records -----------------------------------------------------------------------------------------------------------
+
+RECORD_LINE = re.compile(r"(?P<label>\S.*?) grid=(?P<grid>\d+) lds=(?P<lds>\d+) flags=0x(?P<flags>[0-9a-f]+)")
+
+
+def parse_record(text):
+    lines = [ln for ln in text.split("\n") if ln]
+    out = []
+    for ln in lines:
+        m = RECORD_LINE.fullmatch(ln)
+        assert m, f"malformed launch record line {ln!r}"
+        out.append((m["label"], int(m["grid"]), int(m["lds"]), int(m["flags"], 16)))
+    return out
+
+
+def label_matches(pattern, label):
+    rx = re.escape(pattern).replace(r"\*", r"[^,<>]+")
+    return re.fullmatch(rx, label) is not None
+
+
+def base_name(label):
+    return label.split("<", 1)[0]
+
+
 # ---- GPU cases ----------------------------------------------------------------------------------------------------------------
+
+class Guarded:
+    """a device buffer of `nbytes` inside 0xEE guard regions (`front` / `back` bytes, front a multiple of 16)"""
+
+    def __init__(self, nbytes, back=4096, front=4096):
+        import torch
+
+        self.nbytes, self.front, self.back = int(nbytes), front, back
+        self.t = torch.full((front + self.nbytes + back,), SENTINEL, dtype=torch.uint8, device="cuda")
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.t.data_ptr() + self.front)
+
+    def fetch(self):
+        h = self.t.cpu().numpy()
+        assert (h[: self.front] == SENTINEL).all(), "guard in front of the buffer overwritten"
+        tail = h[self.front + self.nbytes:]
+        assert (tail == SENTINEL).all(), f"guard behind the buffer overwritten at +{int(np.argmax(tail != SENTINEL))}"
+        return h[self.front: self.front + self.nbytes]
+
+
+def packbits(mask):
+    return np.packbits(mask.astype(bool), bitorder="little")
+
 
 def record(L, eng):
     """the launch record of the engine's last call, parsed"""
@@ -181,6 +236,176 @@ def hostile_pack(O, values, c, offset=0):
     view = buf[offset: offset + len(img)]
     assert view.data_ptr() % 16 == offset % 16
     return view
+
+
+def hostile_bitmap(bits, offset=0, front=None):
+    """the canonical bitmap of `bits` -> device tensor of exactly ceil(n/8) bytes, a view with 0xFF bytes directly behind it (and
+    `front` bytes, default 0xFF, before it) that starts `offset` bytes (a multiple of 4) behind a 16-byte boundary"""
+    import torch
+
+    img = packbits(bits)
+    lead = np.full(offset, 0xFF, dtype=np.uint8) if front is None else np.asarray(front, dtype=np.uint8)
+    assert len(lead) % 16 == offset % 16
+    buf = torch.full((16 + len(lead) + len(img) + 64,), 0xFF, dtype=torch.uint8, device="cuda")
+    buf = buf[(-buf.data_ptr()) % 16:]
+    buf[: len(lead)] = torch.from_numpy(lead.copy()).cuda()
+    buf[len(lead): len(lead) + len(img)] = torch.from_numpy(img.copy()).cuda()
+    view = buf[len(lead): len(lead) + len(img)]
+    assert view.data_ptr() % 16 == offset % 16
+    return view, buf
+
+
+def corner_rows(n, R=2048):
+    """rows that carry the corner values (tiles of R rows: 64 lanes x 32 rows): the first four of the first tile, the last four of
+    the last full tile, the last four of the ragged tail (as far as they exist)"""
+    rows = [list(range(min(4, n)))]
+    nfull = n // R
+    if nfull >= 1:
+        rows.append(list(range(nfull * R - 4, nfull * R)))
+    if n % R >= 4 and n > 4:
+        rows.append(list(range(n - 4, n)))
+    return rows
+
+
+def grouped(keys, values, groups, sel=None):
+    """numpy's sum, count, min, max of values per key, in group_aggregate's layout (an empty group: 0, 0, ~0, 0)"""
+    want = np.zeros((groups, 4), dtype=np.uint64)
+    want[:, 2] = (1 << 64) - 1
+    if sel is None:
+        sel = np.ones(len(keys), dtype=bool)
+    k, v = keys[sel].astype(np.int64), values[sel].astype(np.uint64)
+    np.add.at(want[:, 0], k, v)
+    want[:, 1] = np.bincount(k, minlength=groups).astype(np.uint64)
+    np.minimum.at(want[:, 2], k, v)
+    np.maximum.at(want[:, 3], k, v)
+    return want
+
+
+# ---- the runtime of the minimum-alignment and refusal tables (test_min_contract, test_argument_refusals) ----------------------
+
+HOSTILE_BYTES = 256  # 0xFF bytes in front of and behind a mask
+
+
+class Runtime:
+    def __init__(self, L, O):
+        import torch
+
+        from shared_simd_scan_amd import ScanEngine
+
+        self.L, self.O, self.torch = L, O, torch
+        self.default = ScanEngine()
+        self.capped = ScanEngine()  # 4 waves: a wave reaches the tail tile with a previous tile's values still in its LDS
+        self.capped.set_option("grid_cus", 1)
+        self.capped.set_option("max_blocks_per_cu", 1)
+
+    def close(self):
+        self.default.close()
+        self.capped.close()
+
+    def place(self, raw, shift, offset, align):
+        """raw bytes `shift` bytes into a fresh allocation -> (tensor, address of raw[offset]); the address is `align` mod 2 * align"""
+        host = np.concatenate([np.full(shift, 0xFF, dtype=np.uint8), raw])
+        t = self.torch.from_numpy(host).cuda()
+        ptr = t.data_ptr() + shift + offset
+        assert ptr % (2 * align) == align, f"pointer {ptr:#x} is not {align} mod {2 * align}"
+        return t, ptr
+
+    def column(self, model, j, align=16):
+        vals, a = model.columns[j]
+        w = model.case.widths[j]
+        raw = self.O.pack(vals.astype(np.uint32), w)
+        assert (a * w) % 8 == 0
+        return self.place(raw, 0 if w % 2 else align, a * w // 8, align)
+
+    def bitmap(self, model, j, align=16):
+        body = packbits(model.B[j])
+        side = np.full(HOSTILE_BYTES, model.hostile_byte[j], dtype=np.uint8)
+        return self.place(np.concatenate([side, body, side]), align, HOSTILE_BYTES, align)
+
+    def out(self, nbytes, align=16):
+        g = Guarded(nbytes, front=4096 + align)
+        assert g.ptr.value % (2 * align) == align
+        return g
+
+    def word(self):
+        return Guarded(8, back=64, front=64)
+
+
+@pytest.fixture(scope="module")
+def rt(O):
+    """library, oracle, torch and two engines (the default grid and a 4-wave one), closed behind the module's last test"""
+    import torch
+
+    from shared_simd_scan_amd import lib
+
+    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
+    r = Runtime(lib(), O)
+    yield r
+    r.close()
+
+
+# ---- rank processes and the two-rank benchmark (test_sharded_gloo, test_exchange_loopback) ------------------------------------
+
+def free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def join_or_kill(procs, timeout, q=None):
+    """Wait up to `timeout` seconds in all for the rank processes; a rank that failed ends the wait at once (its peers
+    may be blocked in a collective waiting for it).  Survivors are terminated, then killed, before the test fails: a
+    hung rank must not stay on the GPU.  Returns what the ranks put on `q` meanwhile (drained while waiting, so that no
+    child blocks on a full queue at exit)."""
+    deadline = time.monotonic() + timeout
+    got = []
+
+    def drain():
+        while q is not None:
+            try:
+                got.append(q.get_nowait())
+            except queue.Empty:
+                return
+
+    while any(p.is_alive() for p in procs) and time.monotonic() < deadline:
+        drain()
+        if any(p.exitcode not in (None, 0) for p in procs):
+            break
+        time.sleep(0.1)
+    survivors = [p for p in procs if p.is_alive()]
+    for p in survivors:
+        p.terminate()
+    for p in survivors:
+        p.join(10)
+        if p.is_alive():
+            p.kill()
+            p.join(10)
+    for p in procs:
+        p.join(1)
+    drain()
+    codes = [p.exitcode for p in procs]
+    if any(c != 0 for c in codes):
+        msg = f"rank exit codes {codes}"
+        if survivors:
+            msg += f"; {len(survivors)} rank(s) still running after {timeout} s were terminated"
+        reports = [m for m in got if isinstance(m, str)]  # e.g. a rank's traceback
+        pytest.fail("\n".join([msg] + reports))
+    return got
+
+
+def _bench_2ranks(extra_env, extra_args=()):
+    import json
+    import sys
+
+    env = dict(os.environ, BENCH_BACKEND="gloo", **extra_env)
+    env.pop("WORLD_SIZE", None)
+    # --full: the weak partition and the exchange step are not part of a plain run
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "40000000", "--steps", "5",
+                          "--warmup", "2", "--full", *extra_args], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    return res, (json.loads(lines[-1]) if lines else None)
 
 
 # ---- the sources of a feature directory (csrc/<feature>/) -----------------------------------------------------------------------

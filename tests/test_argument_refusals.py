@@ -18,10 +18,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_kernel_paths import SENTINEL, Guarded
-from test_min_contract import rt  # noqa: F401  (the module-scoped runtime fixture: library, oracle, torch, two engines)
+from support import E_INVALID as MI355_E_INVALID
+from support import SENTINEL, Guarded, rt  # noqa: F401  (rt: the module-scoped runtime fixture: library, oracle, torch, two engines)
 
-MI355_E_INVALID = -1
 N, W = 4096, 9
 NB = N // 8
 LT, GT = 2, 4

@@ -10,7 +10,7 @@ of the checked kernel holds rows inside and outside the range.
 
 GPU (-m gpu): every expectation is numpy int64 on the values the test generated (exact under the range rule; "mul" as
 (x * y) * a + k), packed with the oracle's packer; nothing is derived from engine output.  Every one of the ceil(n co / 8) payload
-bytes (trailing bits of the last one included) and the 0xEE guard bytes on both sides of the output (test_kernel_paths.Guarded)
+bytes (trailing bits of the last one included) and the 0xEE guard bytes on both sides of the output (support.Guarded)
 are compared exactly; both inputs must be unchanged after the call; the counter equals numpy's count.  Every case runs in hostile
 surroundings: ones in each column's bits behind row n - 1 and in its pad.  A tile is R = 2048 rows, so the sizes below are the
 smallest that reach one lane, one partial tile, one full tile, a full tile plus one row and many tiles with a ragged tail.
@@ -25,13 +25,11 @@ import re
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, base_name, parse_record
-from test_lookup import corner_rows, grouped
+from support import E_INVALID, SENTINEL, Guarded, L, base_name, corner_rows, eng, fake, grouped, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_arith.h"
-E_INVALID = -1
 LINEAR, MUL = 0, 1
 INT64_MAX, INT64_MIN = (1 << 63) - 1, -(1 << 63)
 
@@ -47,7 +45,7 @@ SIZES = [1, 13, R - 1, R, R + 1, N_BIG]
 
 gpu = pytest.mark.gpu
 
-# corners: up to four (x, y) pairs placed at test_lookup.corner_rows (first tile, last full tile, ragged tail); None: the four
+# corners: up to four (x, y) pairs placed at support.corner_rows (first tile, last full tile, ragged tail); None: the four
 # extremes (0, 0), (X, Y), (X, 0), (0, Y), which reach lo and hi of a linear form
 Recipe = collections.namedtuple("Recipe", "op c1 c2 a b k co corners", defaults=(None,))
 
@@ -762,7 +760,6 @@ def test_graph_capture_and_replay(O, r):
     """one call with its counter in a graph on a side stream: after the inputs' contents change the replay follows them"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
     from shared_simd_scan_amd.engine import PackedColumn
 
     n = N_BIG
@@ -770,50 +767,33 @@ def test_graph_capture_and_replay(O, r):
     miss = miss_of(r.co)
     versions = capture_data(r)
     wants = [expect(r, x, y, miss) for x, y in versions]
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [(plain_pack(O, x, r.c1), plain_pack(O, y, r.c2)) for x, y in versions]
-            col1, col2 = PackedColumn(torch.empty_like(stage[0][0]), n, r.c1), PackedColumn(torch.empty_like(stage[0][1]), n, r.c2)
-            out = Guarded(payload(n, r.co))
-            out_view = out.t[out.front: out.front + out.nbytes]
-            counter = torch.empty(1, dtype=torch.int64, device="cuda")
-            launched = []
 
-            def load(v):
-                col1.data.copy_(stage[v][0])
-                col2.data.copy_(stage[v][1])
-                out.t.fill_(SENTINEL)
-                counter.fill_(-77)
+    def steps(eng):
+        stage = [(plain_pack(O, x, r.c1), plain_pack(O, y, r.c2)) for x, y in versions]
+        col1, col2 = PackedColumn(torch.empty_like(stage[0][0]), n, r.c1), PackedColumn(torch.empty_like(stage[0][1]), n, r.c2)
+        out = Guarded(payload(n, r.co))
+        out_view = out.t[out.front: out.front + out.nbytes]
+        counter = torch.empty(1, dtype=torch.int64, device="cuda")
 
-            def run():
-                eng.arith(r.op, col1, col2, a=r.a, b=r.b, k=r.k, co=r.co, miss=miss, out=out_view, out_of_range=counter)
-                launched[:] = parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())
+        def load(v):
+            col1.data.copy_(stage[v][0])
+            col2.data.copy_(stage[v][1])
+            out.t.fill_(SENTINEL)
+            counter.fill_(-77)
 
-            def check(v, what):
-                assert (out.fetch() == O.pack(wants[v][0], r.co)[: out.nbytes]).all(), what
-                assert int(counter.item()) == wants[v][1], what
+        def run():
+            eng.arith(r.op, col1, col2, a=r.a, b=r.b, k=r.k, co=r.co, miss=miss, out=out_view, out_of_range=counter)
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
+        def check(v, what):
+            assert (out.fetch() == O.pack(wants[v][0], r.co)[: out.nbytes]).all(), what
+            assert int(counter.item()) == wants[v][1], what
+
+        def untouched():
+            assert (out.fetch() == SENTINEL).all() and int(counter.item()) == -77
+
+        def warmed(launched):
             assert [base_name(x[0]) for x in launched] == [fam]
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (out.fetch() == SENTINEL).all() and int(counter.item()) == -77, "ran instead of being recorded"
-            for v in (0, 1, 0):
-                load(v)
-                g.replay()
-                side.synchronize()
-                check(v, f"replay of version {v}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))

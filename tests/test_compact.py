@@ -9,7 +9,7 @@ data recipe is not vacuous.
 GPU (-m gpu): every expectation is numpy on the values and the bitmap the test generated --
 vals[np.unpackbits(bitmap, bitorder="little")[:n].astype(bool)], cut at the capacity and packed with the oracle's packer; the
 count is int(bits.sum()); nothing is derived from engine output.  Every one of the ceil(m c / 8) payload bytes (trailing bits of
-the last one included) and the 0xEE guard bytes on both sides of the output (test_kernel_paths.Guarded) are compared exactly --
+the last one included) and the 0xEE guard bytes on both sides of the output (support.Guarded) are compared exactly --
 the guard behind the payload begins at the very next byte --; column and bitmap must be unchanged after the call.  Every case
 runs in hostile surroundings: ones in the column's bits behind row n - 1 and in its pad, 0xFF bytes directly behind byte
 ceil(n / 8) of the bitmap.  A tile is R = 2048 rows, a chunk K = 16384 rows (one wave's work), a scan group 1024 chunks.
@@ -21,12 +21,11 @@ import os
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
+from support import E_INVALID, SENTINEL, Guarded, L, base_name, eng, fake, hostile_bitmap, hostile_pack, packbits, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_compact.h"
-E_INVALID = -1
 
 # the kernels of csrc/compact/, as the launch record names them: the GPU cases below assert these labels
 EDGES_KERNEL = "compact_edges_kernel"
@@ -64,6 +63,7 @@ def dword_bytes(n, c):
     return (n * c + 31) // 32 * 4
 
 
+# differs from test_top_k's and test_sort_rows' values_of in the seed only ([c, n, salt], theirs end in 7 and 17): the "not vacuous" tests pin each file's data
 @functools.lru_cache(maxsize=None)
 def values_of(c, n, salt=0):
     rng = np.random.default_rng([c, n, salt])
@@ -299,23 +299,6 @@ def test_capture_data_is_not_vacuous(c):
 # ---------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------
-
-def hostile_bitmap(bits, offset=0, front=None):
-    """the canonical bitmap of `bits` -> device tensor of exactly ceil(n/8) bytes, a view with 0xFF bytes directly behind it (and
-    `front` bytes, default 0xFF, before it) that starts `offset` bytes (a multiple of 4) behind a 16-byte boundary"""
-    import torch
-
-    img = packbits(bits)
-    lead = np.full(offset, 0xFF, dtype=np.uint8) if front is None else np.asarray(front, dtype=np.uint8)
-    assert len(lead) % 16 == offset % 16
-    buf = torch.full((16 + len(lead) + len(img) + 64,), 0xFF, dtype=torch.uint8, device="cuda")
-    buf = buf[(-buf.data_ptr()) % 16:]
-    buf[: len(lead)] = torch.from_numpy(lead.copy()).cuda()
-    buf[len(lead): len(lead) + len(img)] = torch.from_numpy(img.copy()).cuda()
-    view = buf[len(lead): len(lead) + len(img)]
-    assert view.data_ptr() % 16 == offset % 16
-    return view, buf
-
 
 def want_record(c, writes=True):
     return PREFIX_KERNELS + [EDGES_KERNEL] + ([COMPACT_KERNEL] if writes else [])
@@ -569,63 +552,46 @@ def test_graph_capture_and_replay(O, c):
     place the replay follows them"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
     from shared_simd_scan_amd.engine import PackedColumn
 
     n = N_BIG
     versions = capture_data(c)
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [(plain_pack(O, v, c), torch.from_numpy(packbits(b)).cuda()) for v, b in versions]
-            col = PackedColumn(torch.empty_like(stage[0][0]), n, c)
-            bitmap = torch.empty_like(stage[0][1])
-            out = Guarded(dword_bytes(n, c), back=4096)
-            view = out.t[out.front: out.front + out.nbytes]
-            cnt = torch.empty(1, dtype=torch.int64, device="cuda")
-            launched = []
 
-            def load(r):
-                col.data.copy_(stage[r][0])
-                bitmap.copy_(stage[r][1])
-                out.t.fill_(SENTINEL)
-                cnt.fill_(-7)
+    def steps(eng):
+        stage = [(plain_pack(O, v, c), torch.from_numpy(packbits(b)).cuda()) for v, b in versions]
+        col = PackedColumn(torch.empty_like(stage[0][0]), n, c)
+        bitmap = torch.empty_like(stage[0][1])
+        out = Guarded(dword_bytes(n, c), back=4096)
+        view = out.t[out.front: out.front + out.nbytes]
+        cnt = torch.empty(1, dtype=torch.int64, device="cuda")
 
-            def run():
-                rc = lib().mi355_compact_dev(eng._ctx, col.data.data_ptr(), n, c, bitmap.data_ptr(), view.data_ptr(), n, cnt.data_ptr())
-                assert rc == 0, lib().mi355_last_error()
-                launched[:] = parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())
+        def load(r):
+            col.data.copy_(stage[r][0])
+            bitmap.copy_(stage[r][1])
+            out.t.fill_(SENTINEL)
+            cnt.fill_(-7)
 
-            def check(r, what):
-                want, count = expect(*versions[r])
-                wb = O.pack(np.ascontiguousarray(want), c)[: payload(count, c)]
-                have = out.fetch()
-                assert int(cnt.item()) == count, what
-                assert (have[: len(wb)] == wb).all() and (have[len(wb):] == SENTINEL).all(), what
+        def run():
+            rc = lib().mi355_compact_dev(eng._ctx, col.data.data_ptr(), n, c, bitmap.data_ptr(), view.data_ptr(), n, cnt.data_ptr())
+            assert rc == 0, lib().mi355_last_error()
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
+        def check(r, what):
+            want, count = expect(*versions[r])
+            wb = O.pack(np.ascontiguousarray(want), c)[: payload(count, c)]
+            have = out.fetch()
+            assert int(cnt.item()) == count, what
+            assert (have[: len(wb)] == wb).all() and (have[len(wb):] == SENTINEL).all(), what
+
+        def untouched():
+            assert (out.fetch() == SENTINEL).all() and int(cnt.item()) == -7
+
+        def warmed(launched):
             assert [base_name(x[0]) for x in launched] == PREFIX_KERNELS + [EDGES_KERNEL, COMPACT_KERNEL]
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (out.fetch() == SENTINEL).all() and int(cnt.item()) == -7, "ran instead of being recorded"
-            for r in (0, 1, 0):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay of version {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))
 
 
 @gpu
@@ -634,49 +600,34 @@ def test_capture_refuses_to_grow_the_workspace(O):
     names graph capture), nothing is enqueued for it and the capture stays intact -- the small call around it replays"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
     from shared_simd_scan_amd.engine import PackedColumn
 
     c, small_n, big_n = 9, K + 77, 40 * K
     vals, bits = values_of(c, small_n), bits_of("random-1/2", small_n)
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            col, bitmap = PackedColumn(plain_pack(O, vals, c), small_n, c), torch.from_numpy(packbits(bits)).cuda()
-            big_col = PackedColumn(plain_pack(O, values_of(c, big_n), c), big_n, c)
-            big_bitmap = torch.from_numpy(packbits(bits_of("random-1/2", big_n))).cuda()
-            out, refused = Guarded(dword_bytes(small_n, c)), Guarded(dword_bytes(big_n, c))
-            cnt = torch.full((2,), -7, dtype=torch.int64, device="cuda")
-            seen = {}
 
-            def run(capturing):
-                assert lib().mi355_compact_dev(eng._ctx, col.data.data_ptr(), small_n, c, bitmap.data_ptr(), out.ptr, small_n, cnt.data_ptr()) == 0
-                if capturing:
-                    seen["rc"] = lib().mi355_compact_dev(eng._ctx, big_col.data.data_ptr(), big_n, c, big_bitmap.data_ptr(), refused.ptr, big_n,
-                                                         cnt.data_ptr() + 8)
-                    seen["msg"] = (lib().mi355_last_error() or b"").decode()
-                    seen["record"] = (lib().mi355_ctx_last_launch(eng._ctx) or b"").decode()
+    def setup(eng):
+        col, bitmap = PackedColumn(plain_pack(O, vals, c), small_n, c), torch.from_numpy(packbits(bits)).cuda()
+        big_col = PackedColumn(plain_pack(O, values_of(c, big_n), c), big_n, c)
+        big_bitmap = torch.from_numpy(packbits(bits_of("random-1/2", big_n))).cuda()
+        out, refused = Guarded(dword_bytes(small_n, c)), Guarded(dword_bytes(big_n, c))
+        cnt = torch.full((2,), -7, dtype=torch.int64, device="cuda")
 
-            run(False)
-            side.synchronize()
+        def small():
+            assert lib().mi355_compact_dev(eng._ctx, col.data.data_ptr(), small_n, c, bitmap.data_ptr(), out.ptr, small_n, cnt.data_ptr()) == 0
+
+        def big():
+            return lib().mi355_compact_dev(eng._ctx, big_col.data.data_ptr(), big_n, c, big_bitmap.data_ptr(), refused.ptr, big_n, cnt.data_ptr() + 8)
+
+        def reset():
             out.t.fill_(SENTINEL)
             cnt.fill_(-7)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run(True)
-            side.synchronize()
-            assert seen["rc"] == E_INVALID and "graph" in seen["msg"] and "captur" in seen["msg"], seen
-            assert seen["record"] == "", seen
-            g.replay()
-            side.synchronize()
+
+        def check_small():
             want, count = expect(vals, bits)
             wb = O.pack(np.ascontiguousarray(want), c)[: payload(count, c)]
             assert cnt.tolist() == [count, -7] and (out.fetch()[: len(wb)] == wb).all()
-            assert (refused.fetch() == SENTINEL).all(), "the refused call wrote to its output"
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return small, big, reset, check_small, refused
+
+    capture.refused_under_capture(setup)

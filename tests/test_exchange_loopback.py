@@ -23,13 +23,12 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from test_sharded_gloo import _bench_2ranks, free_port, join_or_kill
+from support import E_INVALID, _bench_2ranks, free_port, join_or_kill
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "loopback_rccl.cpp")
 LIB = os.path.join(ROOT, "tests", "cpp", "libloopback_rccl.so")
 COMM_SRC = os.path.join(ROOT, "shared_simd_scan_amd", "csrc", "comm.hip")
-E_INVALID = -1
 RANK_TIMEOUT_S = 420  # per test, all ranks together; the stand-in's own socket timeouts are far shorter
 
 

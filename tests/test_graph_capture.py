@@ -1,13 +1,9 @@
 """Graph capture and replay of every device entry point (include/mi355_scan.h "graph capture").
 
-Protocol, one helper (capture_replay) for every case of CAPTURE_CASES: the context lives on the side stream that is captured;
-every buffer exists before the capture; the call runs once eagerly (kernel code loaded, workspace grown) and is checked; it is
-captured on that one stream (a linear chain of nodes: no second stream, no fork / join) with torch's default
-capture_error_mode "global", so an illegal call anywhere ends the capture with an error; after the capture and before the first
-replay every output still holds its 0xEE fill -- the call was recorded, not executed; then three replays, each over inputs that
-were overwritten in place (column, mask, row ids, device-side counts) and outputs refilled with 0xEE, each compared byte for
-byte with numpy inside intact guard bytes.  The three versions' expected outputs differ pairwise (asserted on the CPU), so a
-stale or an accumulated result cannot pass.  Integer work only: every comparison is exact.
+Every case of CAPTURE_CASES goes through the protocol of capture.capture_replay, with a Trial as its buffers: three replays, each
+over inputs that were overwritten in place (column, mask, row ids, device-side counts) and outputs refilled with 0xEE, each
+compared byte for byte with numpy inside intact guard bytes.  The three versions' expected outputs differ pairwise (asserted on
+the CPU), so a stale or an accumulated result cannot pass.  Integer work only: every comparison is exact.
 
 generate_dev, dev_memset and the n = 0 forms take all of their inputs by value: their three replays produce the same bytes, and
 only the 0xEE refill shows that each replay ran (Trial.constant).
@@ -22,7 +18,9 @@ import re
 import numpy as np
 import pytest
 
-from test_kernel_paths import N_SMALL, SENTINEL, Case, Guarded, column, packbits, parse_record
+import capture
+from kernel_cases import N_SMALL, Case, check_select, column
+from support import E_INVALID, SENTINEL, Guarded, packbits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,7 +29,6 @@ N_SELECT = 65536 * 23 + 77     # 24 look-back chunks at c = 9
 MIN_SCAN_GRID = 17
 FRACTIONS = (0.2, 0.35, 0.5)   # share of rows that hold one of the hot keys, per version
 DENSITIES = (0.4, 0.5, 0.6)    # set bits of a mask, per version
-E_INVALID = -1
 AND, OR, XOR, ANDNOT = 0, 1, 2, 3
 EQ, NE, LT, LE, GT, GE, BETWEEN, NOT_BETWEEN = range(8)
 
@@ -287,50 +284,18 @@ def make_ctx(L, stream, opts=()):
     return ctx
 
 
-def last_record(L, ctx):
-    return parse_record((L.mi355_ctx_last_launch(ctx) or b"").decode())
-
-
 def capture_replay(L, O, setup, opts=(), between=None):
-    """the protocol of the module docstring.  setup(T) -> the call (a function that returns one status or a list of them);
-    between(T, r): eager work on the same stream and context in front of replay r"""
-    import torch
+    """capture.capture_replay over a Trial, versions 0, 1, 2.  setup(T) -> the call (a function that returns one status or a list
+    of them); between(T, r): eager work on the same stream and context in front of replay r"""
+    def steps(eng):
+        T = Trial(L, O, eng._ctx)
+        call = setup(T)
+        T.assert_distinct()
+        return capture.Steps(load=T.load, run=lambda: all_ok(L, call()), check=T.check, untouched=lambda: T.untouched(0),
+                             warmed=lambda rec: T.on_record and T.on_record(rec), before_capture=lambda: T.before_capture and T.before_capture(),
+                             between=between and (lambda r: between(T, r)))
 
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        ctx = make_ctx(L, side, opts)
-        g = None
-        try:
-            T = Trial(L, O, ctx)
-            call = setup(T)
-            T.assert_distinct()
-            T.load(0)
-            all_ok(L, call())  # eager: kernel code loaded, occupancy queried, workspace grown
-            side.synchronize()
-            if T.on_record:
-                T.on_record(last_record(L, ctx))
-            T.check(0, "eager warm-up")
-            T.load(0)
-            side.synchronize()
-            if T.before_capture:
-                T.before_capture()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                rcs = call()
-            all_ok(L, rcs)
-            side.synchronize()
-            T.untouched(0)
-            for r in range(3):
-                if between:
-                    between(T, r)
-                T.load(r)
-                g.replay()
-                side.synchronize()
-                T.check(r, "replay")
-        finally:
-            side.synchronize()
-            del g
-            L.mi355_ctx_destroy(ctx)
+    capture.capture_replay(steps, (0, 1, 2), opts)
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------
@@ -749,6 +714,7 @@ def test_captured_pipeline(L, O):
     capture_replay(L, O, setup)
 
 
+# not capture.capture_replay: most outputs are allocated inside the capture, so only `hits` can show "untouched", and the eager ones are refilled by hand
 @gpu
 def test_captured_pipeline_through_the_engine(L, O):
     """the same pipeline through ScanEngine; outputs a method offers no argument for are allocated inside torch.cuda.graph"""
@@ -910,8 +876,6 @@ def test_graph_survives_workspace_growth(L, O):
     mi355_ctx_destroy).  The eager call runs in front of every replay: its own result and the replay's are exact."""
     import torch
 
-    from test_kernel_paths import check_select
-
     class Eng:  # what check_select needs of an engine
         def __init__(self, ctx, stream):
             self._ctx, self.stream = ctx, stream
@@ -985,6 +949,7 @@ def test_replays_interleave_with_eager_calls(L, O):
     capture_replay(L, O, setup, between=between)
 
 
+# not capture.capture_replay: an eager pair in front of the capture, two calls whose divisors are read inside it, eager scans between it and the replays
 @gpu
 def test_llc_decision_is_frozen_at_capture(L):
     """The recorded scan (csrc/llc_repeat.hpp) after a captured call.  It describes the launch that RUNS directly before the next one.  Inside one capture

@@ -11,7 +11,7 @@ the data recipes are not vacuous.
 
 GPU (-m gpu): every expectation is numpy arithmetic on the keys and values the test generated -- np.bincount, np.add.at on
 uint64, np.minimum.at / np.maximum.at over the rows with key < groups -- packed with the oracle's packer on the way in; nothing
-is derived from engine output.  The output and the counter sit inside 0xEE guard bytes (test_kernel_paths.Guarded) that must
+is derived from engine output.  The output and the counter sit inside 0xEE guard bytes (support.Guarded) that must
 stay untouched; inputs and mask must be unchanged after the call.  A tile is 2048 rows (32 rows per lane), so the sizes below
 are the smallest that reach one lane, one partial tile, a tile less one row, one full tile, a full tile plus one row, and many
 tiles with a ragged tail.
@@ -28,12 +28,11 @@ import re
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, record, upload  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, packbits
+from support import E_INVALID, SENTINEL, Guarded, L, eng, fake, packbits, record, upload  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_groupby_wide.h"
-E_INVALID = -1
 U64_MAX = (1 << 64) - 1
 MAX_GROUPS = support.header_macro(HEADER, "MI355_GROUP_WIDE_MAX_GROUPS")  # the header's limit bounds every recipe below
 CU_LDS = 160 * 1024
@@ -709,7 +708,6 @@ def test_graph_capture_and_replay(O):
     replays over keys, values and a mask overwritten in place, the counter of dropped rows included"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine
     from shared_simd_scan_amd.engine import PackedColumn
 
     ck, cv, groups = CAPTURE_SHAPE
@@ -722,53 +720,36 @@ def test_graph_capture_and_replay(O):
     for i in range(3):
         for j in range(i):
             assert (versions[i][3][:, :2] != versions[j][3][:, :2]).any() and versions[i][4] != versions[j][4], "a stale result could pass"
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [[torch.from_numpy(x).cuda() for x in v[:3]] for v in versions]
-            kcol = PackedColumn(torch.empty_like(stage[0][0]), n, ck)
-            vcol = PackedColumn(torch.empty_like(stage[0][1]), n, cv)
-            mask = torch.empty_like(stage[0][2])
-            res, cnt = Guarded(groups * 32), Guarded(8)
-            out = res.t[res.front: res.front + res.nbytes].view(torch.int64).view(groups, 4)
-            dropped = cnt.t[cnt.front: cnt.front + 8].view(torch.int64)
 
-            def load(r):
-                kcol.data.copy_(stage[r][0])
-                vcol.data.copy_(stage[r][1])
-                mask.copy_(stage[r][2])
-                res.t.fill_(SENTINEL)
-                cnt.t.fill_(SENTINEL)
+    def steps(eng):
+        stage = [[torch.from_numpy(x).cuda() for x in v[:3]] for v in versions]
+        kcol = PackedColumn(torch.empty_like(stage[0][0]), n, ck)
+        vcol = PackedColumn(torch.empty_like(stage[0][1]), n, cv)
+        mask = torch.empty_like(stage[0][2])
+        res, cnt = Guarded(groups * 32), Guarded(8)
+        out = res.t[res.front: res.front + res.nbytes].view(torch.int64).view(groups, 4)
+        dropped = cnt.t[cnt.front: cnt.front + 8].view(torch.int64)
 
-            def run():
-                eng.group_aggregate_wide(kcol, vcol, groups, mask=mask, out=out, dropped=dropped)
+        def load(r):
+            kcol.data.copy_(stage[r][0])
+            vcol.data.copy_(stage[r][1])
+            mask.copy_(stage[r][2])
+            res.t.fill_(SENTINEL)
+            cnt.t.fill_(SENTINEL)
 
-            def check(r, what):
-                assert np.array_equal(res.fetch().view(np.uint64).reshape(groups, 4), versions[r][3]), what
-                assert int(cnt.fetch().view(np.uint64)[0]) == versions[r][4], what
+        def run():
+            eng.group_aggregate_wide(kcol, vcol, groups, mask=mask, out=out, dropped=dropped)
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (res.fetch() == SENTINEL).all() and (cnt.fetch() == SENTINEL).all(), "ran instead of being recorded"
-            for r in range(3):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+        def check(r, what):
+            assert np.array_equal(res.fetch().view(np.uint64).reshape(groups, 4), versions[r][3]), what
+            assert int(cnt.fetch().view(np.uint64)[0]) == versions[r][4], what
+
+        def untouched():
+            assert (res.fetch() == SENTINEL).all() and (cnt.fetch() == SENTINEL).all()
+
+        return capture.Steps(load, run, check, untouched)
+
+    capture.capture_replay(steps, range(3))
 
 
 @gpu

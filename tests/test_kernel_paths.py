@@ -13,184 +13,15 @@ import ctypes as C
 import glob
 import os
 import re
+import subprocess
 import zlib
-from dataclasses import dataclass
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "shared_simd_scan_amd", "csrc")
-
-N_SMALL = 10 * 4096 + 77  # ten shared-scan wave tiles (five at 128 values per lane) and a ragged tail
-N_FLUSH = 19_000_077      # 4639 tiles of 4096 rows: 1159 per wave of a 4-wave grid (> 2 x kPackedFlushTiles = 1024)
-N_BYTES = 1_100_077       # 269 tiles: 67 per wave, each at least one step of the linear kernels' 8-bit counters (flush: 31)
-FLUSH_TILES = 1100
-BYTE_STEPS = 62
-SHARED_TILE_ROWS = 4096   # 64 lanes x 64 values: the shared scans' wave tile
-WAVES_PER_BLOCK = 4
-
-LAUNCHER_SET = {0x20000: "short last table attached (shared_linear2_kernel)", 0x100000: "aligned output image (shared_linear_kernel)"}
-# option bits of "kernel_flags" (DESIGN.md section 8): the shared scans' switches and the selection's
-SHARED_BITS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 8192, 16384, 32768, 131072, 262144, 524288, 1048576, 4194304, 8388608]
-SELECT_BITS = [2048, 4096, 2048 + 4096]
-TIMING_ABLATIONS = {512: "selection: no expansion (wrong ids by construction)", 1024: "selection: no look-back (wrong ids by construction)"}
-UNUSED_BITS = {65536: "kernel bit 0x1000: read nowhere (reserved in csrc/switches.hpp: it stays out of the kernels' word)"}
-
-
-@dataclass(frozen=True)
-class Case:
-    id: str
-    op: str                # shared, scan_eq, scan_range, combine, in, scan2, select, decompress, generate, pack_u32,
-                           # bitmap_and, bitmap_count, rowids, gather, aggregate, histogram
-    expect: tuple          # one label pattern per launch, in order ("*" = any one template argument)
-    c: int = 9
-    n: int = N_SMALL
-    P: int = 1
-    layout: int = 0        # shared: 0 per-predicate, 1 linear
-    hits: bool = True
-    opts: tuple = ()       # (("kernel_flags", 32768), ("scan_nt_stores", 1), ...)
-    set_bits: int = 0      # flags bits the (last) launch must carry
-    clear_bits: int = 0    # ... and must not
-    bit: int = 0           # the option bit this case is about: without it the launch record differs
-    column: str = "random"  # "const": every value one key (all hits), "alt": two values alternating
-    min_tiles: int = 0     # grid capped to 4 waves; every wave walks more than this many tiles
-
-    def opt(self, name, default=0):
-        return dict(self.opts).get(name, default)
-
-
-def _cap(*extra):
-    return (("grid_cus", 1), ("max_blocks_per_cu", 1)) + tuple(extra)
-
-
-CASES = [
-    # ---- shared scans, P = 2: two equality decodes; P <= 8: one-pass LUT ------------------------------------------------------
-    Case("pair_pp", "shared", ("shared_pair_kernel<9, 34, 128>",), P=2),
-    Case("pair_linear_nt", "shared", ("shared_pair_kernel<9, 18, 64>",), P=2, layout=1, opts=(("scan_nt_stores", 1),)),
-    Case("pair_bit32_lut", "shared", ("shared_lut_kernel<9, 34, 128, 0, false>",), P=2, opts=(("kernel_flags", 32),), bit=32),
-    Case("lut_pp_vpl128", "shared", ("shared_lut_kernel<9, 34, 128, 0, false>",), P=4),
-    Case("lut_pp_vpl64_opt", "shared", ("shared_lut_kernel<9, 34, 64, 0, false>",), P=4, opts=(("shared_vpl", 64),)),
-    Case("lut_pp", "shared", ("shared_lut_kernel<9, 34, 64, 0, false>",), P=8),
-    Case("lut_pp_nt", "shared", ("shared_lut_kernel<9, 18, 64, 0, false>",), P=8, opts=(("scan_nt_stores", 1),)),
-    Case("lut_pp_plain", "shared", ("shared_lut_kernel<9, 2, 64, 0, false>",), P=8, opts=(("scan_nt_stores", 0),)),
-    Case("lut_linear", "shared", ("shared_lut_kernel<9, 34, 64, 1, false>",), P=8, layout=1),
-    Case("lut_linear_nt", "shared", ("shared_lut_kernel<9, 18, 64, 1, false>",), P=5, layout=1, opts=(("scan_nt_stores", 1),)),
-    Case("lut_linear_plain", "shared", ("shared_lut_kernel<17, 2, 64, 1, false>",), P=7, c=17, layout=1, opts=(("scan_nt_stores", 0),)),
-    # byte-entry multi-pass LUT (linear rows without hit counts)
-    Case("lut_multi_c17", "shared", ("shared_lut_kernel<17, 2, 64, 1, true>",), P=170, c=17, layout=1, hits=False),
-    Case("lut_multi_bit2", "shared", ("shared_lut_kernel<9, 2, 64, 1, true>",), P=12, layout=1, hits=False,
-         opts=(("kernel_flags", 2),), bit=2),
-    # ---- per-predicate, 32 keys per lookup ---------------------------------------------------------------------------------
-    Case("wide3_rc0", "shared", ("shared_wide3_kernel<9, 2, 0, false>",), P=24, hits=False),
-    Case("wide3_rc1", "shared", ("shared_wide3_kernel<9, 2, 1, false>",), P=24),
-    Case("wide3_rc1_nt", "shared", ("shared_wide3_kernel<9, 18, 1, false>",), P=24, opts=(("scan_nt_stores", 1),)),
-    Case("wide3_rc2", "shared", ("shared_wide3_kernel<9, 2, 2, false>",), P=40),
-    Case("wide3_rc0_big", "shared", ("shared_wide3_kernel<17, 2, 0, true>",), P=24, c=17, hits=False),
-    Case("wide3_rc1_big", "shared", ("shared_wide3_kernel<17, 2, 1, true>",), P=24, c=17),
-    Case("wide3_rc2_big", "shared", ("shared_wide3_kernel<17, 2, 2, true>",), P=40, c=17),
-    Case("wide3_rc1_bit8192_bytes", "shared", ("shared_wide3_kernel<17, 2, 1, false>",), P=24, c=17,
-         opts=(("kernel_flags", 8192),), bit=8192),
-    Case("wide3_rc2_c12", "shared", ("shared_wide3_kernel<12, 2, 2, false>",), P=48, c=12),
-    Case("wide3_unused_bit65536", "shared", ("shared_wide3_kernel<9, 2, 2, false>",), P=40, opts=(("kernel_flags", 65536),), bit=65536),
-    Case("chain_bit16384", "shared", ("shared_general_kernel<17, 2, 64>",), P=16, c=17, opts=(("kernel_flags", 16384),), bit=16384),
-    Case("chain_bit64", "shared", ("shared_general_kernel<9, 2, 64>",), P=24, opts=(("kernel_flags", 64),), bit=64),
-    Case("chain_tables_too_big", "shared", ("shared_general_kernel<32, 2, 64>",), P=800, c=32, hits=False, n=4096 + 77),
-    Case("wide2_hist", "shared", ("shared_wide2_kernel<9, 2, 64, 0, false>",), P=64),
-    Case("wide2_hist_nt", "shared", ("shared_wide2_kernel<9, 18, 64, 0, false>",), P=64, opts=(("scan_nt_stores", 1),)),
-    Case("wide2_big", "shared", ("shared_wide2_kernel<17, 2, 64, 0, true>",), P=100, c=17),
-    Case("wide2_bit1_drain", "shared", ("shared_wide2_kernel<9, 2, 64, 0, false>",), P=64, opts=(("kernel_flags", 1),), bit=1),
-    Case("wide2_bit4_rotate", "shared", ("shared_wide2_kernel<9, 2, 64, 0, false>",), P=64, opts=(("kernel_flags", 4),), bit=4),
-    Case("wide2_bit8_reductions", "shared", ("shared_wide2_kernel<9, 2, 64, 0, false>",), P=24, opts=(("kernel_flags", 8),), bit=8),
-    Case("wide2_rc1_bit32768", "shared", ("shared_wide2_kernel<9, 2, 64, 1, false>",), P=24, opts=(("kernel_flags", 32768),), bit=32768),
-    Case("wide2_rc2_bit32768", "shared", ("shared_wide2_kernel<9, 2, 64, 2, false>",), P=40, opts=(("kernel_flags", 32768),), bit=32768),
-    Case("wide_pp_bit2", "shared", ("shared_wide_kernel<9, 2, 64, 0>",), P=24, opts=(("kernel_flags", 2),), bit=2),
-    Case("wide_pp_bit2_nt", "shared", ("shared_wide_kernel<9, 18, 64, 0>",), P=24, opts=(("kernel_flags", 2), ("scan_nt_stores", 1))),
-    Case("wide_pp_bit1_drain", "shared", ("shared_wide_kernel<9, 2, 64, 0>",), P=24, opts=(("kernel_flags", 3),), bit=1),
-    Case("wide_linear_bit2", "shared", ("shared_wide_kernel<9, 2, 64, 1>",), P=24, layout=1, opts=(("kernel_flags", 2),), bit=2),
-    # ---- linear rows ---------------------------------------------------------------------------------------------------------
-    Case("linear_p9", "shared", ("shared_linear_kernel<9, 2, 1>",), P=9, layout=1, clear_bits=0x100000),
-    Case("linear_p16_two_rows", "shared", ("shared_linear_kernel<12, 2, 2>",), P=16, c=12, layout=1),
-    Case("linear_p16_bit16", "shared", ("shared_linear_kernel<12, 2, 1>",), P=16, c=12, layout=1, opts=(("kernel_flags", 16),), bit=16),
-    Case("linear_image", "shared", ("shared_linear_kernel<9, 2, 1>",), P=47, layout=1, set_bits=0x100000),
-    Case("linear_p12_bit256", "shared", ("shared_linear_kernel<9, 2, 1>",), P=12, layout=1, hits=False,
-         opts=(("kernel_flags", 256),), bit=256, clear_bits=0x100000),
-    Case("linear_bit128_c17", "shared", ("shared_linear2_kernel<17, 2>",), P=170, c=17, layout=1, hits=False,
-         opts=(("kernel_flags", 128),), bit=128, set_bits=0x20000),
-    Case("linear_p33_bit131072_image", "shared", ("shared_linear_kernel<9, 2, 1>",), P=33, layout=1,
-         opts=(("kernel_flags", 131072),), bit=131072, set_bits=0x100000),
-    Case("linear_p33_bit262144_no_image", "shared", ("shared_linear_kernel<9, 2, 1>",), P=33, layout=1,
-         opts=(("kernel_flags", 131072 + 262144),), bit=262144, clear_bits=0x100000),
-    Case("linear_p121_bit8388608_image", "shared", ("shared_linear_kernel<9, 2, 1>",), P=121, layout=1,
-         opts=(("kernel_flags", 8388608),), bit=8388608, set_bits=0x100000),
-    Case("linear2_detached", "shared", ("shared_linear2_kernel<9, 2>",), P=12, layout=1, hits=False, clear_bits=0x20000),
-    Case("linear2_attached", "shared", ("shared_linear2_kernel<9, 2>",), P=65, layout=1, set_bits=0x20000),
-    Case("linear2_p33_bit524288", "shared", ("shared_linear2_kernel<9, 2>",), P=33, layout=1,
-         opts=(("kernel_flags", 131072 + 524288),), bit=524288, clear_bits=0x20000),
-    Case("linear_p65_bit1048576_never", "shared", ("shared_linear_kernel<9, 2, 1>",), P=65, layout=1,
-         opts=(("kernel_flags", 1048576),), bit=1048576, clear_bits=0x120000),
-    Case("linear2_p121_bit4194304_always", "shared", ("shared_linear2_kernel<9, 2>",), P=121, layout=1,
-         opts=(("kernel_flags", 4194304),), bit=4194304, set_bits=0x20000),
-    Case("linear3_rc0", "shared", ("shared_linear3_kernel<9, 2, 0, false>",), P=33, layout=1, hits=False),
-    Case("linear3_rc1", "shared", ("shared_linear3_kernel<9, 2, 1, false>",), P=32, layout=1),
-    Case("linear3_rc2", "shared", ("shared_linear3_kernel<9, 2, 2, false>",), P=40, layout=1),
-    Case("linear3_rc2_big", "shared", ("shared_linear3_kernel<17, 2, 2, true>",), P=33, c=17, layout=1),
-    Case("linear3_rc1_bit8192_bytes", "shared", ("shared_linear3_kernel<17, 2, 1, false>",), P=32, c=17, layout=1,
-         opts=(("kernel_flags", 8192),), bit=8192),
-    # ---- packed 16-bit hit counters: every wave flushes at least twice, all hits on one key (worst case) -------------------
-    *[Case(f"flush_wide3_c{c}_p{P}", "shared", (f"shared_wide3_kernel<{c}, 18, 2, {'true' if c == 17 else 'false'}>",), P=P, c=c,
-           n=N_FLUSH, column="const", opts=_cap(), min_tiles=FLUSH_TILES) for c, P in ((9, 33), (9, 48), (9, 63), (17, 33), (17, 48), (17, 64))],
-    Case("flush_wide3_c9_p48_alt", "shared", ("shared_wide3_kernel<9, 18, 2, false>",), P=48, n=N_FLUSH, column="alt", opts=_cap(),
-         min_tiles=FLUSH_TILES),
-    *[Case(f"flush_linear3_p{P}", "shared", ("shared_linear3_kernel<9, 2, 2, false>",), P=P, layout=1, n=N_FLUSH, column="const",
-           opts=_cap(), min_tiles=FLUSH_TILES) for P in (33, 40)],
-    Case("flush_wide2_p33_bit32768", "shared", ("shared_wide2_kernel<9, 18, 64, 2, false>",), P=33, n=N_FLUSH, column="const",
-         opts=_cap(("kernel_flags", 32768)), min_tiles=FLUSH_TILES),
-    # ---- the linear kernels' 8-bit byte counters (flushed every 31 steps), all hits ------------------------------------------
-    Case("bytes_linear_p9", "shared", ("shared_linear_kernel<9, 2, 1>",), P=9, layout=1, n=N_BYTES, column="const", opts=_cap(),
-         min_tiles=BYTE_STEPS),
-    Case("bytes_linear_p16", "shared", ("shared_linear_kernel<9, 2, 1>",), P=16, layout=1, n=N_BYTES, column="const", opts=_cap(),
-         min_tiles=BYTE_STEPS),
-    Case("bytes_linear_p31", "shared", ("shared_linear_kernel<9, 2, 1>",), P=31, layout=1, n=N_BYTES, column="const", opts=_cap(),
-         min_tiles=BYTE_STEPS),
-    Case("bytes_linear2_p65", "shared", ("shared_linear2_kernel<9, 2>",), P=65, layout=1, n=N_BYTES, column="const", opts=_cap(),
-         set_bits=0x20000, min_tiles=BYTE_STEPS),
-    Case("bytes_linear2_p129", "shared", ("shared_linear2_kernel<9, 2>",), P=129, layout=1, n=N_BYTES, column="const", opts=_cap(),
-         set_bits=0x20000, min_tiles=BYTE_STEPS),
-    Case("bytes_linear_p16_c12", "shared", ("shared_linear_kernel<12, 2, 2>",), P=16, c=12, layout=1, n=N_BYTES, column="const",
-         opts=_cap(), min_tiles=BYTE_STEPS),
-    # ---- equality / range scans and their consumers --------------------------------------------------------------------------
-    Case("scan_eq", "scan_eq", ("scan_burst_kernel<9, 0, 34, 128, 4>",)),
-    Case("scan_eq_burst1", "scan_eq", ("scan_burst_kernel<9, 0, 34, 128, 1>",), opts=(("scan_burst", 1),)),
-    Case("scan_eq_nt", "scan_eq", ("scan_burst_kernel<9, 0, 18, 128, 4>",), opts=(("scan_nt_stores", 1),)),
-    Case("scan_eq_plain", "scan_eq", ("scan_burst_kernel<9, 0, 2, 128, 4>",), opts=(("scan_nt_stores", 0),)),
-    Case("scan_eq_dma0", "scan_eq", ("scan_burst_kernel<9, 0, 0, 128, 4>",), opts=(("dma_aux", 0),)),
-    Case("scan_eq_c21", "scan_eq", ("scan_burst_kernel<21, 0, 34, 64, 1>",), c=21),
-    Case("scan_range_c7", "scan_range", ("scan_burst_kernel<7, 1, 34, 128, 1>",), c=7),
-    Case("combine_masked", "combine", ("scan_burst_kernel<9, 1, 34, 128, 4>",)),
-    Case("scan_in", "in", ("in_kernel<9, 34, 128>",), P=20),
-    Case("scan_in_nt", "in", ("in_kernel<9, 18, 128>",), P=20, opts=(("scan_nt_stores", 1),)),
-    Case("scan_in_plain", "in", ("in_kernel<9, 2, 128>",), P=20, opts=(("scan_nt_stores", 0),)),
-    Case("scan2", "scan2", ("scan2_kernel<9, 34, 128>",)),
-    Case("scan2_nt", "scan2", ("scan2_kernel<9, 18, 128>",), opts=(("scan_nt_stores", 1),)),
-    Case("select2", "select", ("select2_kernel<9, 1, 128>",)),
-    Case("select_single", "select", ("select_kernel<9, 1, 128>",), opts=(("select_kernel", 1),)),
-    *[Case(f"select2_bit{b}", "select", ("select2_kernel<9, 1, 128>",), opts=(("kernel_flags", b),), bit=b) for b in SELECT_BITS],
-    *[Case(f"select_single_bit{b}", "select", ("select_kernel<9, 1, 128>",), opts=(("kernel_flags", b), ("select_kernel", 1)), bit=b)
-      for b in SELECT_BITS],
-    Case("decompress", "decompress", ("decompress_kernel<9, 18>",)),
-    Case("decompress_dma0", "decompress", ("decompress_kernel<9, 0>",), opts=(("dma_aux", 0),)),
-    Case("decompress_dma2", "decompress", ("decompress_kernel<9, 2>",), opts=(("dma_aux", 2),)),
-    Case("decompress_dma34", "decompress", ("decompress_kernel<9, 34>",), opts=(("dma_aux", 34),)),
-    Case("generate_splitmix", "generate", ("pack_kernel<3>",)),
-    Case("pack_u32", "pack_u32", ("pack_tiled_kernel<1, 5>",)),
-    Case("bitmap_and", "bitmap_and", ("bitmap_kernel<0>",)),
-    Case("bitmap_count", "bitmap_count", ("bitmap_kernel<4>", "sum_slots_kernel")),
-    Case("rowids", "rowids", ("rowid_count_kernel", "rowid_scan_kernel", "rowid_write_kernel")),
-    Case("gather", "gather", ("gather_kernel",)),
-    Case("aggregate", "aggregate", ("aggregate_init_kernel", "aggregate_kernel<9, 128>")),
-    Case("histogram", "histogram", ("histogram_kernel<9, 128>",)),
-]
+from kernel_cases import (CASES, FLUSH_TILES, LAUNCHER_SET, N_SMALL, SELECT_BITS, SHARED_BITS, SHARED_TILE_ROWS, TIMING_ABLATIONS, UNUSED_BITS,
+                          WAVES_PER_BLOCK, build_binary, check_select, column, dry_run, family_of)
+from support import CSRC, ROOT, SENTINEL, Guarded, base_name, label_matches, packbits, parse_record
 
 EXEMPT_KERNELS = {}  # kernel name -> reason; none today
 
@@ -257,21 +88,6 @@ def case_by_id(cid):
     return next(c for c in CASES if c.id == cid)
 
 
-def base_name(label):
-    return label.split("<", 1)[0]
-
-
-def family_of(label):
-    """the family mi355_shared_scan_kernel / mi355_shared_where_kernel names for the kernel of a launch-record label"""
-    name = base_name(label)
-    if name in ("shared_lut_kernel", "shared_where_lut_kernel") and label.split(">")[0].split(",")[-1].strip() == "true":
-        return name + "(multi-pass)"
-    for stem in ("shared_wide", "shared_linear"):
-        if name.startswith(stem):
-            return stem + "_kernel"
-    return name
-
-
 # ------------------------------------------------------------------------------------------------------------------------
 # CPU: the table covers every kernel, every variant axis and every option bit
 # ------------------------------------------------------------------------------------------------------------------------
@@ -322,10 +138,6 @@ def test_every_variant_has_a_case(pattern, set_bits, clear_bits, what):
 
 def switch_table():
     """csrc/switches.hpp as tests/cpp/launch_dry_run --switches prints it: [(name, option value, kernel-side bit, receiver)]"""
-    import subprocess
-
-    from test_launch_plan import build_binary
-
     out = subprocess.run([build_binary(), "--switches"], capture_output=True, text=True, timeout=60, check=True).stdout
     return [(name, int(opt), int(kbit, 16), recv) for name, opt, kbit, recv in (ln.split("\t") for ln in out.splitlines())]
 
@@ -333,8 +145,6 @@ def switch_table():
 def switch_words(options):
     """[(shared scans' word, selection's word)] of kernel_switch_word() per option value, read from the flags=0x... of the launch
     record of an equality scan (every launch but the selection's carries the shared scans' word) and of a selection"""
-    from test_launch_plan import dry_run
-
     recs = dry_run([(op, 9, 1, 0, 1, N_SMALL, v, 0, -1, 0, 18, 0, 0) for v in options for op in (0, 5)])
     words = [parse_record(text)[0][3] for _, text in recs]
     return list(zip(words[0::2], words[1::2]))
@@ -446,69 +256,6 @@ def test_flush_cases_walk_enough_tiles():
 # ------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ------------------------------------------------------------------------------------------------------------------------
-
-SENTINEL = 0xEE
-RECORD_LINE = re.compile(r"(?P<label>\S.*?) grid=(?P<grid>\d+) lds=(?P<lds>\d+) flags=0x(?P<flags>[0-9a-f]+)")
-
-
-def parse_record(text):
-    lines = [ln for ln in text.split("\n") if ln]
-    out = []
-    for ln in lines:
-        m = RECORD_LINE.fullmatch(ln)
-        assert m, f"malformed launch record line {ln!r}"
-        out.append((m["label"], int(m["grid"]), int(m["lds"]), int(m["flags"], 16)))
-    return out
-
-
-def label_matches(pattern, label):
-    rx = re.escape(pattern).replace(r"\*", r"[^,<>]+")
-    return re.fullmatch(rx, label) is not None
-
-
-class Guarded:
-    """a device buffer of `nbytes` inside 0xEE guard regions (`front` / `back` bytes, front a multiple of 16)"""
-
-    def __init__(self, nbytes, back=4096, front=4096):
-        import torch
-
-        self.nbytes, self.front, self.back = int(nbytes), front, back
-        self.t = torch.full((front + self.nbytes + back,), SENTINEL, dtype=torch.uint8, device="cuda")
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr() + self.front)
-
-    def fetch(self):
-        h = self.t.cpu().numpy()
-        assert (h[: self.front] == SENTINEL).all(), "guard in front of the buffer overwritten"
-        tail = h[self.front + self.nbytes:]
-        assert (tail == SENTINEL).all(), f"guard behind the buffer overwritten at +{int(np.argmax(tail != SENTINEL))}"
-        return h[self.front: self.front + self.nbytes]
-
-
-def packbits(mask):
-    return np.packbits(mask.astype(bool), bitorder="little")
-
-
-def column(case, rng):
-    """values (uint32) and, for shared / in, the key list"""
-    n, c = case.n, case.c
-    top = (1 << c) if c < 32 else (1 << 32)
-    if case.column == "const":
-        v = int(rng.integers(0, top))
-        return np.full(n, v, dtype=np.uint32), [v] * case.P
-    if case.column == "alt":
-        a, b = (int(x) for x in rng.choice(min(top, 1 << 16), 2, replace=False))
-        vals = np.where(np.arange(n) % 2 == 0, a, b).astype(np.uint32)
-        return vals, [a if k % 2 == 0 else b for k in range(case.P)]
-    P = max(case.P, 1)
-    keys = rng.choice(top, P, replace=False) if 2 * P <= top <= (1 << 20) else rng.integers(0, top, P)
-    keys = [int(k) for k in keys]
-    vals = rng.integers(0, top, n, dtype=np.uint64)
-    take = rng.random(n) < 0.7
-    vals[take] = np.asarray(keys, dtype=np.uint64)[rng.integers(0, P, int(take.sum()))]
-    return vals.astype(np.uint32), keys
 
 
 class Runner:
@@ -713,25 +460,6 @@ class Runner:
         self.ok(self.L.mi355_histogram_dev(eng._ctx, C.c_void_p(packed.data_ptr()), case.n, case.c, None, out.ptr))
         self.record(eng)
         assert np.array_equal(out.fetch().view(np.uint64), np.bincount(vals, minlength=1 << case.c).astype(np.uint64))
-
-
-def check_select(L, eng, packed, vals, n, c, op, a, capacity_kind, first_row=1000, check_ids=True, after=None):
-    """mi355_scan_select_dev with >= 4 KiB of guard behind rowids and >= 7 words behind count_dev"""
-    pred = {0: vals == a, 2: vals < a, 4: vals > a}[op]
-    want = np.nonzero(pred)[0].astype(np.uint64) + first_row
-    cap = {"lt": len(want) // 2, "eq": len(want), "gt": len(want) + 100}[capacity_kind]
-    ids, cnt = Guarded(8 * cap, back=4096), Guarded(8, back=64, front=64)
-    rc = L.mi355_scan_select_dev(eng._ctx, C.c_void_p(packed.data_ptr()), n, c, op, a, 0, 0, None, first_row, ids.ptr, cap, cnt.ptr)
-    assert rc == 0, L.mi355_last_error()
-    eng.synchronize()
-    if after:
-        after()
-    got, count = ids.fetch().view(np.uint64), int(cnt.fetch().view(np.uint64)[0])
-    if check_ids:
-        assert count == len(want)
-        k = min(cap, len(want))
-        assert np.array_equal(got[:k], want[:k])
-        assert (ids.t[ids.front + 8 * k: ids.front + 8 * cap].cpu().numpy() == SENTINEL).all(), "ids written beyond the count"
 
 
 # differs from support.L: a missing library is an error here, it is not built

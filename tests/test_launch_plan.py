@@ -3,7 +3,7 @@
 tests/cpp/launch_dry_run.cpp links against csrc/build/width_group_*.o and calls launch_group_N with LaunchReq::choice_out
 set: nothing is launched, the launcher reports the kernel family and writes the launch-record line.
 
-* every case of test_kernel_paths.CASES that passes through the width groups: the recorded label matches `expect`, the flags
+* every case of kernel_cases.CASES that passes through the width groups: the recorded label matches `expect`, the flags
   word carries `set_bits` / `clear_bits`, and the reported family (what mi355_shared_scan_kernel names) is the family of the
   recorded label;
 * every width, every key count, both layouts, with and without hit counts at kernel_flags = 0: reported family == family of
@@ -11,16 +11,8 @@ set: nothing is launched, the launcher reports the kernel family and writes the 
 
 Grids are not asserted: the occupancy queries have no device to ask.
 """
-import glob
-import os
-import subprocess
-
-from test_kernel_paths import CASES, CSRC, N_SMALL, family_of, label_matches, parse_record
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "launch_dry_run.cpp")
-BIN = os.path.join(ROOT, "tests", "cpp", "build", "launch_dry_run")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_cases import CASES, N_SMALL, dry_run, family_of
+from support import label_matches, parse_record
 
 # launch_dry_run.cpp's `op` (dispatch.hpp enum Op) of the cases that go through launch_group_N
 WIDTH_OPS = {"scan_eq": 0, "scan_range": 1, "combine": 1, "shared": 2, "decompress": 3, "in": 4, "select": 5, "scan2": 6}
@@ -29,37 +21,6 @@ FAMILIES = ["shared_lut_kernel", "shared_lut_kernel(multi-pass)", "shared_wide_k
             "shared_pair_kernel"]
 # (c, P, layout, hits) the sweep leaves out, with the reason; none
 SWEEP_EXCLUSIONS = {}
-
-
-def group_objects():
-    return sorted(glob.glob(os.path.join(CSRC, "build", "width_group_*.o")))
-
-
-def build_binary():
-    if len(group_objects()) != 8:
-        from shared_simd_scan_amd import build
-
-        build.build()
-    objs = group_objects()
-    assert len(objs) == 8, objs
-    newest = max(os.path.getmtime(f) for f in [SRC, os.path.join(CSRC, "dispatch.hpp"), os.path.join(CSRC, "switches.hpp")] + objs)
-    if not os.path.exists(BIN) or os.path.getmtime(BIN) < newest:
-        os.makedirs(os.path.dirname(BIN), exist_ok=True)
-        obj = BIN + ".o"  # (compiled on its own: hipcc would read the group objects as HIP sources next to a .cpp)
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O1", "-std=c++17", "-I", CSRC, "-c", SRC, "-o", obj], check=True)
-        subprocess.run([HIPCC, "--offload-arch=gfx950", obj, *objs, "-o", BIN], check=True)
-    return BIN
-
-
-def dry_run(rows):
-    """rows of (op, c, P, layout, hits, n, kernel_flags, shared_vpl, scan_nt_stores, max_blocks_per_cu, dma_aux, scan_burst, select_single)
-    -> [(family index or -1, launch record text)]"""
-    text = "".join(" ".join(str(int(v)) for v in row) + "\n" for row in rows)
-    res = subprocess.run([build_binary()], input=text, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = [ln.split("\t", 1) for ln in res.stdout.splitlines()]
-    assert len(out) == len(rows), (len(out), len(rows))
-    return [(int(fam), rec) for fam, rec in out]
 
 
 def test_kernel_path_cases_without_a_gpu():

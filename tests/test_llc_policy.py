@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_kernel_paths import Guarded, packbits
+from support import Guarded, packbits
 
 MIB = 1 << 20
 GRANULE = 64 * 1024

@@ -10,7 +10,7 @@ recipe is not vacuous.
 GPU (-m gpu): every expectation is numpy on the values and the table the test generated --
 where(v < T, table[minimum(v, T - 1)], miss) -- packed with the oracle's packer; nothing is derived from engine output.  Every
 one of the ceil(n ct / 8) payload bytes (trailing bits of the last one included) and the 0xEE guard bytes on both sides of the
-output (test_kernel_paths.Guarded) are compared exactly; column and table must be unchanged after the call.  Every case runs in
+output (support.Guarded) are compared exactly; column and table must be unchanged after the call.  Every case runs in
 hostile surroundings: ones in the column's bits behind row n - 1 and in its pad, ones in the table's last-byte bits behind value
 T - 1 and in its pad, ones in the table rows no value can reach (T > 2^c).  A tile is R = 2048 rows, so the sizes below are
 the smallest that reach one lane, one partial tile, one full tile, a full tile plus one row and many tiles with a ragged tail.
@@ -23,12 +23,12 @@ import types
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, header_macro, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
+from support import (E_INVALID, SENTINEL, Guarded, L, base_name, corner_rows, eng, fake, grouped, header_macro, hostile_pack, packbits, plain_pack,  # noqa: F401
+                     record)  # (L, eng, fake: fixtures)
 
 HEADER = "mi355_lookup.h"
-E_INVALID = -1
 
 # the kernels of csrc/lookup/, as the launch record names them: the GPU cases below assert these labels
 LDS_KERNEL = "lookup_lds_kernel"
@@ -85,18 +85,6 @@ def miss_of(ct):
 
 def want_family(c, ct, T):
     return LDS_KERNEL if (reach_of(c, T) + 1) * entry_bytes(ct) <= LDS_MAX else GLOBAL_KERNEL
-
-
-def corner_rows(n):
-    """rows that carry the corner values: the first four of the first tile, the last four of the last full tile, the last four
-    of the ragged tail (as far as they exist)"""
-    rows = [list(range(min(4, n)))]
-    nfull = n // R
-    if nfull >= 1:
-        rows.append(list(range(nfull * R - 4, nfull * R)))
-    if n % R >= 4 and n > 4:
-        rows.append(list(range(n - 4, n)))
-    return rows
 
 
 @functools.lru_cache(maxsize=None)
@@ -346,20 +334,6 @@ def chain_data():
     for a in (kind, year, fk, amount):
         a.setflags(write=False)
     return kind, year, fk, amount
-
-
-def grouped(keys, values, groups, sel=None):
-    """numpy's sum, count, min, max of values per key, in group_aggregate's layout (an empty group: 0, 0, ~0, 0)"""
-    want = np.zeros((groups, 4), dtype=np.uint64)
-    want[:, 2] = (1 << 64) - 1
-    if sel is None:
-        sel = np.ones(len(keys), dtype=bool)
-    k, v = keys[sel].astype(np.int64), values[sel].astype(np.uint64)
-    np.add.at(want[:, 0], k, v)
-    want[:, 1] = np.bincount(k, minlength=groups).astype(np.uint64)
-    np.minimum.at(want[:, 2], k, v)
-    np.maximum.at(want[:, 3], k, v)
-    return want
 
 
 def test_chain_data_is_not_vacuous():
@@ -689,7 +663,6 @@ def test_graph_capture_and_replay(O, case):
     follows the new table"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
     from shared_simd_scan_amd.engine import PackedColumn
 
     c, ct, T = case
@@ -698,51 +671,36 @@ def test_graph_capture_and_replay(O, case):
     miss = miss_of(ct)
     fk, amount, tables = capture_data(c, ct, T)
     wants = [grouped(expect(fk, t, T, miss), amount, 1 << ct) for t in tables]
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [plain_pack(O, t, ct) for t in tables]
-            table = PackedColumn(torch.empty_like(stage[0]), T, ct)
-            fact, values = PackedColumn(plain_pack(O, fk, c), n, c), PackedColumn(plain_pack(O, amount, 17), n, 17)
-            keys = Guarded(payload(n, ct), back=4096)  # the looked-up column; the guard behind stands for the column's pad
-            keys_view = keys.t[keys.front: keys.front + keys.nbytes]
-            agg = torch.empty((1 << ct, 4), dtype=torch.int64, device="cuda")
-            launched = []
 
-            def load(r):
-                table.data.copy_(stage[r])
-                keys.t.fill_(SENTINEL)
-                agg.fill_(-7)
+    def steps(eng):
+        stage = [plain_pack(O, t, ct) for t in tables]
+        table = PackedColumn(torch.empty_like(stage[0]), T, ct)
+        fact, values = PackedColumn(plain_pack(O, fk, c), n, c), PackedColumn(plain_pack(O, amount, 17), n, 17)
+        keys = Guarded(payload(n, ct), back=4096)  # the looked-up column; the guard behind stands for the column's pad
+        keys_view = keys.t[keys.front: keys.front + keys.nbytes]
+        agg = torch.empty((1 << ct, 4), dtype=torch.int64, device="cuda")
+        launched = []
 
-            def run():
-                by = eng.lookup(fact, table, miss=miss, out=keys_view)
-                launched[:] = parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())
-                eng.group_aggregate(by, values, out=agg)
+        def load(r):
+            table.data.copy_(stage[r])
+            keys.t.fill_(SENTINEL)
+            agg.fill_(-7)
 
-            def check(r, what):
-                assert (keys.fetch() == O.pack(expect(fk, tables[r], T, miss), ct)[: keys.nbytes]).all(), what
-                assert (agg.cpu().numpy().view(np.uint64) == wants[r]).all(), what
+        def run():
+            by = eng.lookup(fact, table, miss=miss, out=keys_view)
+            launched[:] = capture.last_record(eng)  # the lookup's: the chain's last call is the aggregate
+            eng.group_aggregate(by, values, out=agg)
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
+        def check(r, what):
+            assert (keys.fetch() == O.pack(expect(fk, tables[r], T, miss), ct)[: keys.nbytes]).all(), what
+            assert (agg.cpu().numpy().view(np.uint64) == wants[r]).all(), what
+
+        def untouched():
+            assert (keys.fetch() == SENTINEL).all() and (agg == -7).all()
+
+        def warmed(_):
             assert [base_name(x[0]) for x in launched] == [fam]
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (keys.fetch() == SENTINEL).all() and (agg == -7).all(), "ran instead of being recorded"
-            for r in (0, 1, 0):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay of version {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))

@@ -35,7 +35,9 @@ from dataclasses import dataclass
 import numpy as np
 import pytest
 
-from test_kernel_paths import SENTINEL, SHARED_TILE_ROWS, Guarded, base_name, family_of, packbits, parse_record
+from kernel_cases import SHARED_TILE_ROWS, family_of
+from support import E_INVALID as MI355_E_INVALID
+from support import HOSTILE_BYTES, SENTINEL, Guarded, base_name, packbits, parse_record, rt  # noqa: F401  (rt: the module-scoped runtime fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -44,10 +46,8 @@ HIST_WIDTHS = (1, 5, 9, 12, 14)
 DECOMPRESS_TILE_ROWS = 4096   # decompress_kernel: 16 steps of 256 values
 ROWID_CHUNK_ROWS = 16384      # rowid_*_kernel: 2048 bitmap bytes per wave
 HOSTILE_ROWS = 256            # at least this many hostile rows in front of a view (and a whole tile + this many behind)
-HOSTILE_BYTES = 256           # 0xFF bytes in front of and behind a mask
 FIRST_ROW = (1 << 32) + 12345  # selection / gather: row ids above 2^32
 FILLS = ("match", "miss")
-MI355_E_INVALID = -1
 
 EQ, NE, LT, LE, GT, GE, BETWEEN, NOT_BETWEEN = range(8)
 AND, OR, XOR, ANDNOT = range(4)
@@ -567,51 +567,6 @@ def np_pack(vals, c, size):
     return out
 
 
-class Runtime:
-    def __init__(self, L, O):
-        import torch
-
-        from shared_simd_scan_amd import ScanEngine
-
-        self.L, self.O, self.torch = L, O, torch
-        self.default = ScanEngine()
-        self.capped = ScanEngine()  # 4 waves: a wave reaches the tail tile with a previous tile's values still in its LDS
-        self.capped.set_option("grid_cus", 1)
-        self.capped.set_option("max_blocks_per_cu", 1)
-
-    def close(self):
-        self.default.close()
-        self.capped.close()
-
-    def place(self, raw, shift, offset, align):
-        """raw bytes `shift` bytes into a fresh allocation -> (tensor, address of raw[offset]); the address is `align` mod 2 * align"""
-        host = np.concatenate([np.full(shift, 0xFF, dtype=np.uint8), raw])
-        t = self.torch.from_numpy(host).cuda()
-        ptr = t.data_ptr() + shift + offset
-        assert ptr % (2 * align) == align, f"pointer {ptr:#x} is not {align} mod {2 * align}"
-        return t, ptr
-
-    def column(self, model, j, align=16):
-        vals, a = model.columns[j]
-        w = model.case.widths[j]
-        raw = self.O.pack(vals.astype(np.uint32), w)
-        assert (a * w) % 8 == 0
-        return self.place(raw, 0 if w % 2 else align, a * w // 8, align)
-
-    def bitmap(self, model, j, align=16):
-        body = packbits(model.B[j])
-        side = np.full(HOSTILE_BYTES, model.hostile_byte[j], dtype=np.uint8)
-        return self.place(np.concatenate([side, body, side]), align, HOSTILE_BYTES, align)
-
-    def out(self, nbytes, align=16):
-        g = Guarded(nbytes, front=4096 + align)
-        assert g.ptr.value % (2 * align) == align
-        return g
-
-    def word(self):
-        return Guarded(8, back=64, front=64)
-
-
 def u64(g):
     return int(g.fetch().view(np.uint64)[0])
 
@@ -785,18 +740,6 @@ def run_pack(rt, eng, case, n):
     eng.synchronize()
     want = np_pack(vals.astype(np.uint64) & np.uint64(vmax(c)), c, size)
     assert np.array_equal(out.fetch(), want), f"{case.id}, n = {n}: packed bytes differ"
-
-
-@pytest.fixture(scope="module")
-def rt(O):
-    import torch
-
-    from shared_simd_scan_amd import lib
-
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    r = Runtime(lib(), O)
-    yield r
-    r.close()
 
 
 @pytest.mark.gpu

@@ -7,7 +7,7 @@ with a message.
 
 GPU (-m gpu): every expectation is numpy int64 arithmetic on the values the test generated -- d = v1 - v2 compared with the
 Python constants -- packed with the oracle's packer on the way in and np.packbits on the way out; nothing is derived from
-engine output.  Output buffers sit inside 0xEE guard bytes (test_kernel_paths.Guarded) that must stay untouched.
+engine output.  Output buffers sit inside 0xEE guard bytes (support.Guarded) that must stay untouched.
 """
 import ctypes as C
 import functools
@@ -16,13 +16,12 @@ import operator
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, record  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, packbits
+from support import E_INVALID, SENTINEL, Guarded, L, eng, fake, packbits, record  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_columns.h"
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
-E_INVALID = -1
 OPS = ["==", "!=", "<", "<=", ">", ">=", "between", "not_between"]
 CMP = {"==": operator.eq, "!=": operator.ne, "<": operator.lt, "<=": operator.le, ">": operator.gt, ">=": operator.ge}
 MASK_OPS = ["and", "or", "xor", "andnot"]
@@ -391,7 +390,6 @@ def test_graph_capture_and_replay(O):
     three replays over columns and a mask overwritten in place"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine
     from shared_simd_scan_amd.engine import PackedColumn
 
     n, c1, c2 = N_BIG, 9, 12
@@ -402,49 +400,32 @@ def test_graph_capture_and_replay(O):
         want = expect(d, "<", 0) & bits
         versions.append((O.pack(v1.astype(np.uint32), c1), O.pack(v2.astype(np.uint32), c2), packbits(bits), packbits(want), int(want.sum())))
     assert len({v[4] for v in versions}) == 3  # a stale result cannot pass
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [[torch.from_numpy(x).cuda() for x in v[:3]] for v in versions]
-            col1 = PackedColumn(torch.empty_like(stage[0][0]), n, c1)
-            col2 = PackedColumn(torch.empty_like(stage[0][1]), n, c2)
-            mask = torch.empty_like(stage[0][2])
-            bm = Guarded((n + 7) // 8)
-            hits = torch.empty(1, dtype=torch.int64, device="cuda")
-            out = bm.t[bm.front: bm.front + bm.nbytes]
 
-            def load(r):
-                col1.data.copy_(stage[r][0])
-                col2.data.copy_(stage[r][1])
-                mask.copy_(stage[r][2])
-                bm.t.fill_(SENTINEL)
-                hits.view(torch.uint8).fill_(SENTINEL)
+    def steps(eng):
+        stage = [[torch.from_numpy(x).cuda() for x in v[:3]] for v in versions]
+        col1 = PackedColumn(torch.empty_like(stage[0][0]), n, c1)
+        col2 = PackedColumn(torch.empty_like(stage[0][1]), n, c2)
+        mask = torch.empty_like(stage[0][2])
+        bm = Guarded((n + 7) // 8)
+        hits = torch.empty(1, dtype=torch.int64, device="cuda")
+        out = bm.t[bm.front: bm.front + bm.nbytes]
 
-            def run():
-                eng.scan_columns(col1, "<", col2, mask=mask, bitmap=out, hits=hits)
+        def load(r):
+            col1.data.copy_(stage[r][0])
+            col2.data.copy_(stage[r][1])
+            mask.copy_(stage[r][2])
+            bm.t.fill_(SENTINEL)
+            hits.view(torch.uint8).fill_(SENTINEL)
 
-            def check(r, what):
-                assert np.array_equal(bm.fetch(), versions[r][3]) and int(hits.item()) == versions[r][4], what
+        def run():
+            eng.scan_columns(col1, "<", col2, mask=mask, bitmap=out, hits=hits)
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (bm.fetch() == SENTINEL).all() and (hits.cpu().numpy().view(np.uint8) == SENTINEL).all(), "ran instead of being recorded"
-            for r in range(3):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+        def check(r, what):
+            assert np.array_equal(bm.fetch(), versions[r][3]) and int(hits.item()) == versions[r][4], what
+
+        def untouched():
+            assert (bm.fetch() == SENTINEL).all() and (hits.cpu().numpy().view(np.uint8) == SENTINEL).all()
+
+        return capture.Steps(load, run, check, untouched)
+
+    capture.capture_replay(steps, range(3))

@@ -52,7 +52,7 @@ def test_launcher_reports_the_planned_divisor():
     """through launch_group_N itself (tests/cpp/launch_dry_run.cpp with its two trailing columns): the divisors of the rule's comment.
     The dry run passes no bitmap, so the budgets are the comment's less the 1e9-row bitmap's 119.2 MiB, rounded down to whole MiB
     where the divisor stays: 70 / 85 / 100 / 120 MiB give 17 / 13 / 11 / 9 (1.125e9 bytes of column over the budget, rounded up, made odd)."""
-    from test_launch_plan import build_binary as build_dry_run
+    from kernel_cases import build_binary as build_dry_run
 
     n, MIB = 10**9, 1 << 20
     col = (n * 9 + 7) // 8

@@ -10,7 +10,7 @@ the data recipe is not vacuous.
 GPU (-m gpu): every expectation is numpy on the values and the set the test generated -- res = (v < m) & set[min(v, m - 1)]
 (all zero when m == 0), XOR negate, AND mask -- packed with the oracle's packer on the way in; nothing is derived from engine
 output.  Every byte of the bitmap (tail bits included), the hit count and the 0xEE guard bytes on both sides of the bitmap
-(test_kernel_paths.Guarded) are compared exactly; set, mask and column must be unchanged after the call.  Tiles are 8192 rows
+(support.Guarded) are compared exactly; set, mask and column must be unchanged after the call.  Tiles are 8192 rows
 at c <= 16 and 4096 above, so the sizes below are the smallest that reach one lane, one partial tile, one full tile, a full
 tile plus one row and many tiles with a ragged tail.
 """
@@ -21,12 +21,11 @@ import types
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, header_macro, record, upload  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
+from support import E_INVALID, SENTINEL, Guarded, L, base_name, eng, fake, header_macro, packbits, record, upload  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_semijoin.h"
-E_INVALID = -1
 
 # the kernels of csrc/semijoin/, as the launch record names them: the GPU cases below assert these labels
 LDS_KERNEL = "semijoin_lds_kernel"
@@ -712,7 +711,6 @@ def test_graph_capture_and_replay(O, case):
     the replay follows the new set"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
     from shared_simd_scan_amd.engine import PackedColumn
 
     c, m = case
@@ -720,51 +718,36 @@ def test_graph_capture_and_replay(O, case):
     fam = LDS_KERNEL if reach_of(c, m) <= LDS_MAX else GLOBAL_KERNEL
     fk, attrs = capture_data(c, m)
     versions = [(O.pack(attr, 5), star_selection(attr, fk, m)) for attr in attrs]
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [torch.from_numpy(v[0]).cuda() for v in versions]
-            dim = PackedColumn(torch.empty_like(stage[0]), m, 5)
-            fact = PackedColumn(upload(O, fk, c), n, c)
-            dim_bitmap = torch.empty((m + 7) // 8, dtype=torch.uint8, device="cuda")
-            dim_hits = torch.empty(1, dtype=torch.int64, device="cuda")
-            res = Guarded((n + 7) // 8)
-            out = res.t[res.front: res.front + res.nbytes]
-            hits_box = []
 
-            def load(r):
-                dim.data.copy_(stage[r])
-                dim_bitmap.fill_(0xFF)
-                res.t.fill_(SENTINEL)
+    def steps(eng):
+        stage = [torch.from_numpy(v[0]).cuda() for v in versions]
+        dim = PackedColumn(torch.empty_like(stage[0]), m, 5)
+        fact = PackedColumn(upload(O, fk, c), n, c)
+        dim_bitmap = torch.empty((m + 7) // 8, dtype=torch.uint8, device="cuda")
+        dim_hits = torch.empty(1, dtype=torch.int64, device="cuda")
+        res = Guarded((n + 7) // 8)
+        out = res.t[res.front: res.front + res.nbytes]
+        hits_box = []
 
-            def run():
-                eng.scan_where("==", 3, dim, bitmap=dim_bitmap, hits=dim_hits)
-                hits_box[:] = [eng.semi_join(fact, dim_bitmap, m, bitmap=out)[1]]
+        def load(r):
+            dim.data.copy_(stage[r])
+            dim_bitmap.fill_(0xFF)
+            res.t.fill_(SENTINEL)
 
-            def check(r, what):
-                want = versions[r][1]
-                assert (res.fetch() == packbits(want)).all() and int(hits_box[0].item()) == int(want.sum()), what
+        def run():
+            eng.scan_where("==", 3, dim, bitmap=dim_bitmap, hits=dim_hits)
+            hits_box[:] = [eng.semi_join(fact, dim_bitmap, m, bitmap=out)[1]]
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
-            assert base_name(parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())[-1][0]) == fam
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (res.fetch() == SENTINEL).all(), "ran instead of being recorded"
-            for r in (0, 1, 0):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay of version {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+        def check(r, what):
+            want = versions[r][1]
+            assert (res.fetch() == packbits(want)).all() and int(hits_box[0].item()) == int(want.sum()), what
+
+        def untouched():  # (the hit count is allocated by the call: it has no state from before the capture)
+            assert (res.fetch() == SENTINEL).all()
+
+        def warmed(launched):
+            assert base_name(launched[-1][0]) == fam
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))

@@ -5,9 +5,6 @@ uses the HIP engine); what is under test is the product's sharding logic: row-ra
 hit-count reduction, ragged last shard.
 """
 import os
-import queue
-import socket
-import time
 
 import numpy as np
 import pytest
@@ -15,54 +12,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def join_or_kill(procs, timeout, q=None):
-    """Wait up to `timeout` seconds in all for the rank processes; a rank that failed ends the wait at once (its peers
-    may be blocked in a collective waiting for it).  Survivors are terminated, then killed, before the test fails: a
-    hung rank must not stay on the GPU.  Returns what the ranks put on `q` meanwhile (drained while waiting, so that no
-    child blocks on a full queue at exit)."""
-    deadline = time.monotonic() + timeout
-    got = []
-
-    def drain():
-        while q is not None:
-            try:
-                got.append(q.get_nowait())
-            except queue.Empty:
-                return
-
-    while any(p.is_alive() for p in procs) and time.monotonic() < deadline:
-        drain()
-        if any(p.exitcode not in (None, 0) for p in procs):
-            break
-        time.sleep(0.1)
-    survivors = [p for p in procs if p.is_alive()]
-    for p in survivors:
-        p.terminate()
-    for p in survivors:
-        p.join(10)
-        if p.is_alive():
-            p.kill()
-            p.join(10)
-    for p in procs:
-        p.join(1)
-    drain()
-    codes = [p.exitcode for p in procs]
-    if any(c != 0 for c in codes):
-        msg = f"rank exit codes {codes}"
-        if survivors:
-            msg += f"; {len(survivors)} rank(s) still running after {timeout} s were terminated"
-        reports = [m for m in got if isinstance(m, str)]  # e.g. a rank's traceback
-        pytest.fail("\n".join([msg] + reports))
-    return got
+from support import _bench_2ranks, free_port, join_or_kill
 
 
 def test_shard_rows_partition():
@@ -332,21 +282,6 @@ def test_missing_librccl_is_an_error_not_a_crash():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, "-c", code], env=env, cwd=root, capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr
-
-
-def _bench_2ranks(extra_env, extra_args=()):
-    import json
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, BENCH_BACKEND="gloo", **extra_env)
-    env.pop("WORLD_SIZE", None)
-    # --full: the weak partition and the exchange step are not part of a plain run
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "40000000", "--steps", "5",
-                          "--warmup", "2", "--full", *extra_args], env=env, cwd=root, capture_output=True, text=True, timeout=600)
-    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
-    return res, (json.loads(lines[-1]) if lines else None)
 
 
 @pytest.mark.gpu

@@ -11,38 +11,18 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_SIZES, GOLDEN_WIDTHS
+from kernel_cases import WHERE_CHAIN as CHAIN
+from kernel_cases import WHERE_COUNT_CASES as COUNT_CASES
+from kernel_cases import WHERE_LUT as LUT
+from kernel_cases import WHERE_LUT_MULTI as LUT_MULTI
+from kernel_cases import WHERE_SINGLE as SINGLE
+from support import E_INVALID
 
 pytestmark = pytest.mark.gpu
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 OPS = ["==", "!=", "<", "<=", ">", ">=", "between", "not_between"]
 GUARD = 256
-E_INVALID = -1
-
-LUT, LUT_MULTI, CHAIN, SINGLE = ("shared_where_lut_kernel", "shared_where_lut_kernel(multi-pass)", "shared_where_chain_kernel",
-                                 "scan_burst_kernel")
-
-
-def expected_family(c, P):
-    """the documented dispatch, written down independently of the launcher: P = 1 the single-
-    predicate scan; c <= 16: tables while ceil(P/8) tables of max(2^c, 4) bytes (rounded up to 16) fit into 160 KiB beside
-    four tiles of 64 x 64 values (whole KiB each), 4 KiB of hit counters and 512 bytes; the compare chain elsewhere"""
-    if P == 1:
-        return SINGLE
-    if c > 16:
-        return CHAIN
-    if P <= 8:
-        return LUT
-    tables = ((P + 7) // 8 * max(1 << c, 4) + 15) // 16 * 16
-    tile = (64 * 64 * c // 8 + 1023) // 1024 * 1024
-    return LUT_MULTI if tables + 4 * tile + 4096 + 512 <= 160 * 1024 else CHAIN
-
-
-# the case table of test_predicate_counts: (c, P, kernel family the call must launch).  tests/test_shared_where_cpu.py holds
-# it against the __global__ kernels of csrc/predicates/.
-COUNT_WIDTHS = [5, 9, 12, 16, 17, 32]
-COUNT_PS = [1, 2, 3, 5, 8, 9, 16, 33, 64, 65, 257, 1024]
-COUNT_CASES = [(c, P, expected_family(c, P)) for c in COUNT_WIDTHS for P in COUNT_PS]
 
 
 def bits(buf, n):

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from kernel_cases import WHERE_COUNT_CASES
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRED_DIR = os.path.join(ROOT, "shared_simd_scan_amd", "csrc", "predicates")
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
@@ -26,19 +28,17 @@ def global_kernels():
 
 def test_every_predicates_kernel_has_a_case():
     """the contract of test_kernel_paths.test_every_kernel_has_a_case for the new directory: every __global__ under
-    csrc/predicates/ is the expected kernel of at least one case of the GPU file's table, and the table names no kernel
-    that does not exist"""
-    import test_shared_where as gpu_file
-
+    csrc/predicates/ is the expected kernel of at least one case of the GPU file's table (kernel_cases.WHERE_COUNT_CASES), and the
+    table names no kernel that does not exist"""
     kernels = global_kernels()
     assert kernels, "no __global__ kernel found under csrc/predicates/"
-    named = {family.split("(")[0] for _, _, family in gpu_file.COUNT_CASES}
+    named = {family.split("(")[0] for _, _, family in WHERE_COUNT_CASES}
     assert kernels <= named, f"kernels without a case: {sorted(kernels - named)}"
     assert named - kernels == {"scan_burst_kernel"}, f"cases name unknown kernels: {sorted(named - kernels)}"
     scan_hpp = open(os.path.join(ROOT, "shared_simd_scan_amd", "csrc", "kernels", "scan.hpp")).read()
     assert re.search(r"__global__[^;{]*?\bvoid\s+scan_burst_kernel\s*\(", scan_hpp)
     # both forms of the table kernel occur
-    fams = {family for _, _, family in gpu_file.COUNT_CASES}
+    fams = {family for _, _, family in WHERE_COUNT_CASES}
     assert {"shared_where_lut_kernel", "shared_where_lut_kernel(multi-pass)", "shared_where_chain_kernel"} <= fams
 
 

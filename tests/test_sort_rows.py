@@ -22,13 +22,11 @@ import os
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
-from test_compact import hostile_bitmap
-from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
+from support import E_INVALID, SENTINEL, Guarded, L, base_name, eng, fake, hostile_bitmap, hostile_pack, packbits, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_sort.h"
-E_INVALID = -1
 
 # the kernels of csrc/sort/, as the launch record names them: the GPU cases below assert these labels
 COUNT_KERNEL = "sort_count_kernel"
@@ -71,6 +69,8 @@ def want_record(c, writes=True):
     return names
 
 
+# values_of and mask_of differ from test_compact's and test_top_k's in the seeds ([.., 17] and [.., 19] here), mask_of also in the kinds it knows:
+# the "not vacuous" tests pin each file's data
 @functools.lru_cache(maxsize=None)
 def values_of(c, n, salt=0):
     rng = np.random.default_rng([c, n, salt, 17])
@@ -609,62 +609,45 @@ def test_graph_capture_and_replay(O, c):
     place the replay follows them"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
 
     n = N_PAT
     versions = capture_data(c)
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [(plain_pack(O, v, c), torch.from_numpy(packbits(m)).cuda()) for v, m in versions]
-            col, mask = torch.empty_like(stage[0][0]), torch.empty_like(stage[0][1])
-            ids, vals = Guarded(n * 8), Guarded(n * 4)
-            cnt = torch.empty(1, dtype=torch.int64, device="cuda")
-            launched = []
 
-            def load(r):
-                col.copy_(stage[r][0])
-                mask.copy_(stage[r][1])
-                ids.t.fill_(SENTINEL)
-                vals.t.fill_(SENTINEL)
-                cnt.fill_(-7)
+    def steps(eng):
+        stage = [(plain_pack(O, v, c), torch.from_numpy(packbits(m)).cuda()) for v, m in versions]
+        col, mask = torch.empty_like(stage[0][0]), torch.empty_like(stage[0][1])
+        ids, vals = Guarded(n * 8), Guarded(n * 4)
+        cnt = torch.empty(1, dtype=torch.int64, device="cuda")
 
-            def run():
-                rc = lib().mi355_sort_rows_dev(eng._ctx, col.data_ptr(), n, c, mask.data_ptr(), 0, 0, ids.ptr, vals.ptr, n, cnt.data_ptr())
-                assert rc == 0, lib().mi355_last_error()
-                launched[:] = parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())
+        def load(r):
+            col.copy_(stage[r][0])
+            mask.copy_(stage[r][1])
+            ids.t.fill_(SENTINEL)
+            vals.t.fill_(SENTINEL)
+            cnt.fill_(-7)
 
-            def check(r, what):
-                rows, v = expect(versions[r][0], False, versions[r][1])
-                q = len(rows)
-                have_ids, have_vals = ids.fetch().view(np.uint64), vals.fetch().view(np.uint32)
-                assert cnt.tolist() == [q], what
-                assert (have_ids[:q] == rows.astype(np.uint64)).all() and (have_ids[q:] == GUARD64).all(), what
-                assert (have_vals[:q] == v).all() and (have_vals[q:] == GUARD32).all(), what
+        def run():
+            rc = lib().mi355_sort_rows_dev(eng._ctx, col.data_ptr(), n, c, mask.data_ptr(), 0, 0, ids.ptr, vals.ptr, n, cnt.data_ptr())
+            assert rc == 0, lib().mi355_last_error()
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
+        def check(r, what):
+            rows, v = expect(versions[r][0], False, versions[r][1])
+            q = len(rows)
+            have_ids, have_vals = ids.fetch().view(np.uint64), vals.fetch().view(np.uint32)
+            assert cnt.tolist() == [q], what
+            assert (have_ids[:q] == rows.astype(np.uint64)).all() and (have_ids[q:] == GUARD64).all(), what
+            assert (have_vals[:q] == v).all() and (have_vals[q:] == GUARD32).all(), what
+
+        def untouched():
+            assert (ids.fetch() == SENTINEL).all() and (vals.fetch() == SENTINEL).all() and cnt.tolist() == [-7]
+
+        def warmed(launched):
             assert [base_name(x[0]) for x in launched] == want_record(c)
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (ids.fetch() == SENTINEL).all() and cnt.tolist() == [-7], "ran instead of being recorded"
-            for r in (0, 1, 0):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay of version {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))
 
 
 @gpu
@@ -673,44 +656,30 @@ def test_capture_refuses_to_grow_the_workspace(O):
     names graph capture), nothing is enqueued for it and the capture stays intact -- the small call around it replays"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
 
     c, small_n, big_n = 9, S + 77, 40 * S
     vals = values_of(c, small_n, salt=13)
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            col, big_col = plain_pack(O, vals, c), plain_pack(O, values_of(c, big_n), c)
-            ids, refused = Guarded(small_n * 8), Guarded(big_n * 8)
-            cnt = torch.full((2,), -7, dtype=torch.int64, device="cuda")
-            seen = {}
 
-            def run(capturing):
-                assert lib().mi355_sort_rows_dev(eng._ctx, col.data_ptr(), small_n, c, None, 1, 0, ids.ptr, None, small_n, cnt.data_ptr()) == 0
-                if capturing:
-                    seen["rc"] = lib().mi355_sort_rows_dev(eng._ctx, big_col.data_ptr(), big_n, c, None, 1, 0, refused.ptr, None, big_n, cnt.data_ptr() + 8)
-                    seen["msg"] = (lib().mi355_last_error() or b"").decode()
-                    seen["record"] = (lib().mi355_ctx_last_launch(eng._ctx) or b"").decode()
+    def setup(eng):
+        col, big_col = plain_pack(O, vals, c), plain_pack(O, values_of(c, big_n), c)
+        ids, refused = Guarded(small_n * 8), Guarded(big_n * 8)
+        cnt = torch.full((2,), -7, dtype=torch.int64, device="cuda")
 
-            run(False)
-            side.synchronize()
+        def small():
+            assert lib().mi355_sort_rows_dev(eng._ctx, col.data_ptr(), small_n, c, None, 1, 0, ids.ptr, None, small_n, cnt.data_ptr()) == 0
+
+        def big():
+            return lib().mi355_sort_rows_dev(eng._ctx, big_col.data_ptr(), big_n, c, None, 1, 0, refused.ptr, None, big_n, cnt.data_ptr() + 8)
+
+        def reset():
             ids.t.fill_(SENTINEL)
             cnt.fill_(-7)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run(True)
-            side.synchronize()
-            assert seen["rc"] == E_INVALID and "graph" in seen["msg"] and "captur" in seen["msg"], seen
-            assert seen["record"] == "", seen
-            g.replay()
-            side.synchronize()
+
+        def check_small():
             rows, _ = expect(vals, True)
             assert cnt.tolist() == [small_n, -7] and (ids.fetch().view(np.uint64) == rows.astype(np.uint64)).all()
-            assert (refused.fetch() == SENTINEL).all(), "the refused call wrote to its output"
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return small, big, reset, check_small, refused
+
+    capture.refused_under_capture(setup)

@@ -21,13 +21,11 @@ import os
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, hostile_pack, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
-from test_compact import hostile_bitmap
-from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
+from support import E_INVALID, SENTINEL, Guarded, L, base_name, eng, fake, hostile_bitmap, hostile_pack, packbits, plain_pack, record  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_topk.h"
-E_INVALID = -1
 
 # the kernels of csrc/topk/, as the launch record names them: the GPU cases below assert these labels
 HIST_KERNEL = "topk_hist_kernel"
@@ -67,6 +65,8 @@ def digits_of(x, c):
     return [(int(x) >> (DIGIT * (D - 1 - d))) & ((1 << DIGIT) - 1 if d else (1 << (c - DIGIT * (D - 1))) - 1) for d in range(D)]
 
 
+# values_of and mask_of differ from test_compact's and test_sort_rows' in the seeds ([.., 7] and [.., 11] here), mask_of also in its "in-place" and "ones"
+# kinds: the "not vacuous" tests pin each file's data
 @functools.lru_cache(maxsize=None)
 def values_of(c, n, salt=0):
     rng = np.random.default_rng([c, n, salt, 7])
@@ -648,59 +648,42 @@ def test_graph_capture_and_replay(O, c):
     place the replay follows them"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
 
     n, k = N_PAT, 1000
     versions = capture_data(c)
     nb = (n + 7) // 8
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [(plain_pack(O, v, c), torch.from_numpy(packbits(m)).cuda()) for v, m in versions]
-            col, mask = torch.empty_like(stage[0][0]), torch.empty_like(stage[0][1])
-            out = Guarded(nb)
-            res = torch.empty(4, dtype=torch.int64, device="cuda")
-            launched = []
 
-            def load(r):
-                col.copy_(stage[r][0])
-                mask.copy_(stage[r][1])
-                out.t.fill_(SENTINEL)
-                res.fill_(-7)
+    def steps(eng):
+        stage = [(plain_pack(O, v, c), torch.from_numpy(packbits(m)).cuda()) for v, m in versions]
+        col, mask = torch.empty_like(stage[0][0]), torch.empty_like(stage[0][1])
+        out = Guarded(nb)
+        res = torch.empty(4, dtype=torch.int64, device="cuda")
 
-            def run():
-                rc = lib().mi355_top_k_dev(eng._ctx, col.data_ptr(), n, c, mask.data_ptr(), k, 1, out.ptr, res.data_ptr())
-                assert rc == 0, lib().mi355_last_error()
-                launched[:] = parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())
+        def load(r):
+            col.copy_(stage[r][0])
+            mask.copy_(stage[r][1])
+            out.t.fill_(SENTINEL)
+            res.fill_(-7)
 
-            def check(r, what):
-                bits, want = expect(versions[r][0], k, True, versions[r][1])
-                assert res.tolist() == want, what
-                assert (out.fetch() == packbits(bits)).all(), what
+        def run():
+            rc = lib().mi355_top_k_dev(eng._ctx, col.data_ptr(), n, c, mask.data_ptr(), k, 1, out.ptr, res.data_ptr())
+            assert rc == 0, lib().mi355_last_error()
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
+        def check(r, what):
+            bits, want = expect(versions[r][0], k, True, versions[r][1])
+            assert res.tolist() == want, what
+            assert (out.fetch() == packbits(bits)).all(), what
+
+        def untouched():
+            assert (out.fetch() == SENTINEL).all() and res.tolist() == [-7] * 4
+
+        def warmed(launched):
             assert [base_name(x[0]) for x in launched] == [HIST_KERNEL, PICK_KERNEL] * passes(c) + [EMIT_KERNEL, SCAN_KERNEL, TRIM_KERNEL]
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (out.fetch() == SENTINEL).all() and res.tolist() == [-7] * 4, "ran instead of being recorded"
-            for r in (0, 1, 0):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay of version {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))
 
 
 @gpu
@@ -709,44 +692,30 @@ def test_capture_refuses_to_grow_the_workspace(O):
     names graph capture), nothing is enqueued for it and the capture stays intact -- the small call around it replays"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
 
     c, small_n, big_n, k = 9, K + 77, 40 * K, 100
     vals = values_of(c, small_n, salt=9)
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            col, big_col = plain_pack(O, vals, c), plain_pack(O, values_of(c, big_n), c)
-            out, refused = Guarded((small_n + 7) // 8), Guarded((big_n + 7) // 8)
-            res = torch.full((8,), -7, dtype=torch.int64, device="cuda")
-            seen = {}
 
-            def run(capturing):
-                assert lib().mi355_top_k_dev(eng._ctx, col.data_ptr(), small_n, c, None, k, 1, out.ptr, res.data_ptr()) == 0
-                if capturing:
-                    seen["rc"] = lib().mi355_top_k_dev(eng._ctx, big_col.data_ptr(), big_n, c, None, k, 1, refused.ptr, res.data_ptr() + 32)
-                    seen["msg"] = (lib().mi355_last_error() or b"").decode()
-                    seen["record"] = (lib().mi355_ctx_last_launch(eng._ctx) or b"").decode()
+    def setup(eng):
+        col, big_col = plain_pack(O, vals, c), plain_pack(O, values_of(c, big_n), c)
+        out, refused = Guarded((small_n + 7) // 8), Guarded((big_n + 7) // 8)
+        res = torch.full((8,), -7, dtype=torch.int64, device="cuda")
 
-            run(False)
-            side.synchronize()
+        def small():
+            assert lib().mi355_top_k_dev(eng._ctx, col.data_ptr(), small_n, c, None, k, 1, out.ptr, res.data_ptr()) == 0
+
+        def big():
+            return lib().mi355_top_k_dev(eng._ctx, big_col.data_ptr(), big_n, c, None, k, 1, refused.ptr, res.data_ptr() + 32)
+
+        def reset():
             out.t.fill_(SENTINEL)
             res.fill_(-7)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run(True)
-            side.synchronize()
-            assert seen["rc"] == E_INVALID and "graph" in seen["msg"] and "captur" in seen["msg"], seen
-            assert seen["record"] == "", seen
-            g.replay()
-            side.synchronize()
+
+        def check_small():
             bits, want = expect(vals, k, True)
             assert res.tolist() == want + [-7] * 4 and (out.fetch() == packbits(bits)).all()
-            assert (refused.fetch() == SENTINEL).all(), "the refused call wrote to its output"
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return small, big, reset, check_small, refused
+
+    capture.refused_under_capture(setup)

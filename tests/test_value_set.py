@@ -18,12 +18,11 @@ import functools
 import numpy as np
 import pytest
 
+import capture
 import support
-from support import L, eng, fake, header_macro, hostile_pack, record, upload  # noqa: F401  (L, eng, fake: fixtures)
-from test_kernel_paths import SENTINEL, Guarded, base_name, packbits, parse_record
+from support import E_INVALID, SENTINEL, Guarded, L, base_name, eng, fake, header_macro, hostile_pack, packbits, record, upload  # noqa: F401  (L, eng, fake: fixtures)
 
 HEADER = "mi355_distinct.h"
-E_INVALID = -1
 
 # the kernels of csrc/distinct/, as the launch record names them: the GPU cases below assert these labels
 LDS_KERNEL = "value_set_lds_kernel"
@@ -917,7 +916,7 @@ def test_graph_capture_and_replay(O):
     contents change the replay follows them"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
     from shared_simd_scan_amd.engine import PackedColumn
 
     c, ct = CAPTURE_CASE
@@ -928,60 +927,45 @@ def test_graph_capture_and_replay(O):
         u, inverse = np.unique(vals, return_inverse=True)
         versions.append((O.pack(vals, c), expect(vals, m), inverse, len(u)))
     assert versions[0][3] != versions[1][3] and (versions[0][2] != versions[1][2]).any(), "a stale result could pass"
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            stage = [torch.from_numpy(v[0]).cuda() for v in versions]
-            col = PackedColumn(torch.empty_like(stage[0]), n, c)
-            sbuf = SetBuffer(m)
-            table = torch.empty(lib().mi355_compressed_buffer_size(ct, m), dtype=torch.uint8, device="cuda")
-            codes = Guarded((n * ct + 7) // 8, back=4096)
-            counts = torch.empty(2, dtype=torch.int64, device="cuda")
-            box = []
 
-            def load(r):
-                col.data.copy_(stage[r])
-                sbuf.fill()
-                table.fill_(0xFF)
-                codes.t.fill_(SENTINEL)
-                counts.fill_(-7)
+    def steps(eng):
+        stage = [torch.from_numpy(v[0]).cuda() for v in versions]
+        col = PackedColumn(torch.empty_like(stage[0]), n, c)
+        sbuf = SetBuffer(m)
+        table = torch.empty(lib().mi355_compressed_buffer_size(ct, m), dtype=torch.uint8, device="cuda")
+        codes = Guarded((n * ct + 7) // 8, back=4096)
+        counts = torch.empty(2, dtype=torch.int64, device="cuda")
+        box = []
 
-            def run():
-                vset, _ = eng.value_set(col, m, out=sbuf.view, counts=counts)
-                tab, tc = eng.set_ranks(vset, m, ct, miss=(1 << ct) - 1, out=table)
-                eng.lookup(col, tab, miss=(1 << ct) - 1, out=codes.t[codes.front:])
-                box[:] = [tc]
+        def load(r):
+            col.data.copy_(stage[r])
+            sbuf.fill()
+            table.fill_(0xFF)
+            codes.t.fill_(SENTINEL)
+            counts.fill_(-7)
 
-            def check(r, what):
-                packed, (sbytes, distinct, outside), inverse, d = versions[r]
-                assert (sbuf.fetch() == sbytes).all() and counts.tolist() == [distinct, outside] and distinct == d, what
-                assert box[0].tolist() == [d, 0], what
-                assert (O.decompress(codes.fetch(), n, ct).astype(np.int64)[:n] == inverse).all(), what
+        def run():
+            vset, _ = eng.value_set(col, m, out=sbuf.view, counts=counts)
+            tab, tc = eng.set_ranks(vset, m, ct, miss=(1 << ct) - 1, out=table)
+            eng.lookup(col, tab, miss=(1 << ct) - 1, out=codes.t[codes.front:])
+            box[:] = [tc]
 
-            load(0)
-            run()
-            side.synchronize()
-            check(0, "eager warm-up")
-            names = [base_name(r[0]) for r in parse_record((lib().mi355_ctx_last_launch(eng._ctx) or b"").decode())]
+        def check(r, what):
+            packed, (sbytes, distinct, outside), inverse, d = versions[r]
+            assert (sbuf.fetch() == sbytes).all() and counts.tolist() == [distinct, outside] and distinct == d, what
+            assert box[0].tolist() == [d, 0], what
+            assert (O.decompress(codes.fetch(), n, ct).astype(np.int64)[:n] == inverse).all(), what
+
+        def untouched():
+            assert (codes.fetch() == SENTINEL).all() and counts.tolist() == [-7, -7]
+
+        def warmed(launched):  # the record of the chain's last call
+            names = [base_name(r[0]) for r in launched]
             assert names and names[0].startswith("lookup_")
-            load(0)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run()
-            side.synchronize()
-            assert (codes.fetch() == SENTINEL).all() and counts.tolist() == [-7, -7], "ran instead of being recorded"
-            for r in (0, 1, 0):
-                load(r)
-                g.replay()
-                side.synchronize()
-                check(r, f"replay of version {r}")
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return capture.Steps(load, run, check, untouched, warmed)
+
+    capture.capture_replay(steps, (0, 1, 0))
 
 
 @gpu
@@ -990,45 +974,31 @@ def test_capture_refuses_to_grow_the_workspace(O):
     graph capture), nothing is enqueued for it and the capture stays intact -- the small call around it replays"""
     import torch
 
-    from shared_simd_scan_amd import ScanEngine, lib
+    from shared_simd_scan_amd import lib
 
     ct, small_m, big_m = 9, M_RANKS, 40 * M_RANKS
     bits = rank_set("random", small_m)
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        eng = ScanEngine(0, stream=side)
-        g = None
-        try:
-            sset = torch.from_numpy(packbits(bits)).cuda()
-            big_set = torch.zeros((big_m + 7) // 8, dtype=torch.uint8, device="cuda")
-            out, refused = Guarded((small_m * ct + 7) // 8), Guarded((big_m * ct + 7) // 8)
-            cnt = torch.full((4,), -7, dtype=torch.int64, device="cuda")
-            seen = {}
 
-            def run(capturing):
-                assert lib().mi355_set_ranks_dev(eng._ctx, sset.data_ptr(), small_m, ct, 0, out.ptr, cnt.data_ptr()) == 0
-                if capturing:
-                    seen["rc"] = lib().mi355_set_ranks_dev(eng._ctx, big_set.data_ptr(), big_m, ct, 0, refused.ptr, cnt.data_ptr() + 16)
-                    seen["msg"] = (lib().mi355_last_error() or b"").decode()
-                    seen["record"] = (lib().mi355_ctx_last_launch(eng._ctx) or b"").decode()
+    def setup(eng):
+        sset = torch.from_numpy(packbits(bits)).cuda()
+        big_set = torch.zeros((big_m + 7) // 8, dtype=torch.uint8, device="cuda")
+        out, refused = Guarded((small_m * ct + 7) // 8), Guarded((big_m * ct + 7) // 8)
+        cnt = torch.full((4,), -7, dtype=torch.int64, device="cuda")
 
-            run(False)
-            side.synchronize()
+        def small():
+            assert lib().mi355_set_ranks_dev(eng._ctx, sset.data_ptr(), small_m, ct, 0, out.ptr, cnt.data_ptr()) == 0
+
+        def big():
+            return lib().mi355_set_ranks_dev(eng._ctx, big_set.data_ptr(), big_m, ct, 0, refused.ptr, cnt.data_ptr() + 16)
+
+        def reset():
             out.t.fill_(SENTINEL)
             cnt.fill_(-7)
-            side.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                run(True)
-            side.synchronize()
-            assert seen["rc"] == E_INVALID and "graph" in seen["msg"] and "captur" in seen["msg"], seen
-            assert seen["record"] == "", seen
-            g.replay()
-            side.synchronize()
+
+        def check_small():
             entries, members, unfit = rank_table(bits, ct, 0)
             assert cnt.tolist() == [members, unfit, -7, -7] and (out.fetch() == O.pack(entries, ct)[:out.nbytes]).all()
-            assert (refused.fetch() == SENTINEL).all(), "the refused call wrote to its output"
-        finally:
-            side.synchronize()
-            del g
-            eng.close()
+
+        return small, big, reset, check_small, refused
+
+    capture.refused_under_capture(setup)

@@ -137,6 +137,12 @@ HEADERS["mi355_distinct.h"] = [
     ("mi355_set_ranks_dev", _int, [_vp, _vp, _u64, C.c_uint, _u32, _vp, _vp]),
 ]
 
+# the row of every key of a column, as the packed table lookup reads.  (In front of mi355_sort.h too.)
+HEADERS["mi355_keyindex.h"] = [
+    ("mi355_key_index_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _u64, _int, _vp, _u64, C.c_uint, _u32, _vp]),
+    ("mi355_key_index_kernel", C.c_char_p, [C.c_uint, _u64]),
+]
+
 # the row ids of a column in value order
 HEADERS["mi355_sort.h"] = [
     ("mi355_sort_rows_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _int, _u64, _vp, _vp, _u64, _vp]),

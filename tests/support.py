@@ -1,6 +1,7 @@
 """What the test files share: where things are, the library and engine fixtures, what a public header declares, a recording
-stand-in for the library, launch records, guarded buffers, packed and hostile uploads, the runtime of the alignment tables, the
-rank-process helpers, and the checks every feature header and feature source directory gets.  capture.py (graph capture) and
+stand-in for the library, launch records, guarded buffers and the exact image of one, packed and hostile uploads, the runtime of
+the alignment tables, the rank-process helpers, the checks every feature header and feature source directory gets, and which entry
+points' launchers reach a piece of the context's state.  capture.py (graph capture) and
 kernel_cases.py (the kernel-path case table) stand beside it; no test file imports from another test file.
 
 A plain module, not a conftest: a test file imports what it uses by name, fixtures included (pytest takes an imported fixture as
@@ -198,6 +199,42 @@ class Guarded:
         tail = h[self.front + self.nbytes:]
         assert (tail == SENTINEL).all(), f"guard behind the buffer overwritten at +{int(np.argmax(tail != SENTINEL))}"
         return h[self.front: self.front + self.nbytes]
+
+
+class Expected:
+    """a Guarded output and every byte a call must leave in it: `body` is the whole buffer as the call leaves it, SENTINEL where it
+    must not write.  The buffer and its image (guards, body, guards) are made on the device at the first reset(); check() compares
+    them there in one pass and fetches the buffer only to say where they differ"""
+
+    def __init__(self, body):
+        self.want = np.ascontiguousarray(body, dtype=np.uint8)
+        self.g = self.image = None
+
+    @property
+    def ptr(self):
+        return self.g.ptr if len(self.want) else None
+
+    def reset(self):
+        import torch
+
+        if self.g is None:
+            self.g = Guarded(len(self.want))
+            guard = lambda k: np.full(k, SENTINEL, dtype=np.uint8)
+            self.image = torch.from_numpy(np.concatenate([guard(self.g.front), self.want, guard(self.g.back)])).cuda()
+        self.g.t.fill_(SENTINEL)
+
+    def untouched(self):
+        return bool((self.g.t == SENTINEL).all().item())
+
+    def check(self, what):
+        import torch
+
+        if torch.equal(self.g.t, self.image):
+            return
+        have = self.g.fetch()  # (asserts the guard bytes on both sides)
+        bad = np.nonzero(have != self.want)[0]
+        assert bad.size == 0, (what, "byte", int(bad[0]), "of", len(have), "have", int(have[bad[0]]), "want", int(self.want[bad[0]]), "wrong bytes", int(bad.size))
+        raise AssertionError((what, "the buffer and its image differ, but not in a byte"))
 
 
 def packbits(mask):
@@ -420,6 +457,37 @@ def global_kernels_of(feature):
     for path in feature_sources(feature):
         kernels |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", open(path).read()))
     return kernels
+
+
+def hip_functions():
+    """[(name, file, body)] of every function a .hip file under csrc/ defines at file level: a definition's line starts in column 0
+    and ends with its argument list, `{` and `}` stand alone in column 0 (the sources' one style; the parse fails loudly below where
+    a file has a `{` line it did not match)"""
+    found = []
+    for path in sorted(glob.glob(os.path.join(CSRC, "**", "*.hip"), recursive=True)):
+        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(path).read(), flags=re.S)
+        defs = list(re.finditer(r"^(?![ \t#}])[^\n;{}]*?\b(\w+)\((?:[^;{}]*?)\)\n(?:#[^\n]*\n)*\{\n(.*?)\n\}", text, flags=re.M | re.S))
+        opened = [m for m in re.finditer(r"^\{$", text, flags=re.M)]
+        assert len(defs) == len(opened), f"{os.path.relpath(path, ROOT)}: {len(opened)} bodies, {len(defs)} parsed"
+        for m in defs:
+            found.append((m.group(1), os.path.relpath(path, CSRC), m.group(2)))
+    return found
+
+
+def entry_points_reaching(*needles):
+    """every exported mi355_*_dev whose launcher source mentions one of `needles`: in its own body, or in that of a function it calls
+    -- a helper of its translation unit or another entry point -- to any depth; sorted"""
+    funcs = hip_functions()
+    reach = {(name, path) for name, path, body in funcs if any(s in body for s in needles)}
+    while True:
+        more = {(name, path) for name, path, body in funcs if (name, path) not in reach
+                and any(re.search(rf"\b{callee}\s*(?:<[^;()]*>)?\(", body) for callee, where in reach if callee.startswith("mi355_") or where == path)}
+        if not more:
+            break
+        reach |= more
+    reach = {name for name, _ in reach}
+    exported = {s for header in sorted(os.listdir(INCLUDE)) if header.endswith(".h") for s in declared(header)}
+    return sorted(s for s in reach & exported if s.endswith("_dev"))
 
 
 def gpu_part_of(test_file):

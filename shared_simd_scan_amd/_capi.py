@@ -143,6 +143,15 @@ HEADERS["mi355_keyindex.h"] = [
     ("mi355_key_index_kernel", C.c_char_p, [C.c_uint, _u64]),
 ]
 
+# prefix sums and differences of a packed column.  (In front of mi355_sort.h too.)
+HEADERS["mi355_running.h"] = [
+    ("mi355_running_sum_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_int64, C.c_int64, C.c_uint, C.c_uint, _u32, _vp, _vp, _vp]),
+    ("mi355_running_sum_kernel", C.c_char_p, [C.c_uint, _u64, C.c_int64, C.c_int64, C.c_uint]),
+    ("mi355_running_sum_workspace_words", _u64, [_u64]),
+    ("mi355_delta_dev", _int, [_vp, _vp, _u64, C.c_uint, _u32, C.c_int64, C.c_uint, _u32, _vp, _vp]),
+    ("mi355_delta_kernel", C.c_char_p, [C.c_uint, C.c_int64, C.c_uint]),
+]
+
 # the row ids of a column in value order
 HEADERS["mi355_sort.h"] = [
     ("mi355_sort_rows_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _int, _u64, _vp, _vp, _u64, _vp]),

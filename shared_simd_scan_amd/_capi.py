@@ -152,6 +152,15 @@ HEADERS["mi355_running.h"] = [
     ("mi355_delta_kernel", C.c_char_p, [C.c_uint, C.c_int64, C.c_uint]),
 ]
 
+# a packed column's runs as two packed columns, and their expansion.  (In front of mi355_sort.h too.)
+HEADERS["mi355_runs.h"] = [
+    ("mi355_run_encode_dev", _int, [_vp, _vp, _u64, C.c_uint, C.c_uint, _vp, _vp, _u64, _vp, _vp]),
+    ("mi355_run_encode_kernel", C.c_char_p, [C.c_uint, C.c_uint]),
+    ("mi355_run_encode_workspace_words", _u64, [_u64]),
+    ("mi355_run_decode_dev", _int, [_vp, _vp, C.c_uint, _vp, C.c_uint, _u64, _vp, _u64, _u32, _vp, _vp]),
+    ("mi355_run_decode_kernel", C.c_char_p, [C.c_uint, C.c_uint]),
+]
+
 # the row ids of a column in value order
 HEADERS["mi355_sort.h"] = [
     ("mi355_sort_rows_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, _int, _u64, _vp, _vp, _u64, _vp]),

@@ -307,6 +307,42 @@ def delta_kernel(c: int, k: int = 0, co: Optional[int] = None) -> str:
     return s.decode()
 
 
+def run_encode_workspace_words(n: int) -> int:
+    """64-bit words of workspace ScanEngine.run_encode needs for n rows (mi355_run_encode_workspace_words; arithmetic only)"""
+    return int(lib().mi355_run_encode_workspace_words(_unsigned(n, 1 << 64, "n {}")))
+
+
+def run_encode_kernel(c: int, ce: int) -> str:
+    """the emitting kernel of ScanEngine.run_encode (mi355_run_encode_kernel; arithmetic only, needs no device).  A width outside
+    1..32 -> ValueError"""
+    s = lib().mi355_run_encode_kernel(int(c), int(ce)) if all(0 <= int(w) < 1 << 32 for w in (c, ce)) else None
+    if s is None:
+        raise ValueError((c, ce))
+    return s.decode()
+
+
+def run_decode_kernel(cv: int, ce: int) -> str:
+    """the kernel of ScanEngine.run_decode (mi355_run_decode_kernel; arithmetic only, needs no device).  A width outside 1..32 ->
+    ValueError"""
+    s = lib().mi355_run_decode_kernel(int(cv), int(ce)) if all(0 <= int(w) < 1 << 32 for w in (cv, ce)) else None
+    if s is None:
+        raise ValueError((cv, ce))
+    return s.decode()
+
+
+def _ends_width(n: int, ends_width: Optional[int]) -> int:
+    """the width of a column of run ends over n rows: the one that holds n itself (None), or the caller's when it does"""
+    n = _unsigned(n, 1 << 32, "n {} beyond 2^32 - 1 rows: an end of at most 32 bits cannot hold it")
+    if ends_width is None:
+        return max(1, n.bit_length())
+    ce = int(ends_width)
+    if not 1 <= ce <= 32:
+        raise ValueError(f"ends_width {ce} outside 1..32")
+    if n > (1 << ce) - 1:
+        raise ValueError(f"n {n} beyond 2^{ce} - 1: an end of {ce} bits cannot hold it")
+    return ce
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     """an optional tensor as a pointer argument: None travels as NULL"""
     return t.data_ptr() if t is not None else None
@@ -690,6 +726,91 @@ class ScanEngine:
         counter = self._int64()
         self.delta(col, first=first, k=0, co=col.c, out_of_range=counter)
         return counter
+
+    def run_encode(self, col: PackedColumn, capacity: Optional[int] = None, ends_width: Optional[int] = None, values=None, ends=None,
+                   count: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+        """the runs of `col` -> (values, ends, count int64[1]): row i is a run's last row when i == n - 1 or x_i != x_{i+1}; `values`
+        is a packed column's data at col.c bits with every run's value, `ends` one at ends_width bits with the row behind every
+        run's last row, both in row order.  At most `capacity` runs are written (default col.n); count is always the number of
+        runs.  ends_width=None: the width that holds n.  `values` / `ends`: uint8 device tensors of at least
+        compressed_buffer_size(width, capacity) bytes that overlap nothing else (allocated when None); False: that output is not
+        computed (values only is SELECT DISTINCT of a sorted column, ends only its group boundaries; None is returned in its
+        place).  `workspace` as in running_sum.  delta(ends, first=0) is the run lengths (run_lengths), running_sum(lengths) the
+        ends again; lookup(arith(ends - 1), running_sum(y)) -> delta is sum(y) per run.  Nothing synchronises.  Capturable into a
+        graph whatever its arguments and without a warm-up call (pass the outputs, `count` and `workspace`); the column is read at
+        every replay."""
+        n = col.n
+        ce = _ends_width(n, ends_width)
+        capacity = _unsigned(n if capacity is None else capacity, 1 << 64, "capacity {}")
+        most = min(capacity, n)
+        if capacity and values is False and ends is False:
+            raise ValueError("neither values nor ends asked for with capacity > 0")
+        if values is not False:
+            values = self._packed_out(values, col.c, most, (most * col.c + 31) // 32 * 4)  # whole dwords
+        if ends is not False:
+            ends = self._packed_out(ends, ce, most, (most * ce + 31) // 32 * 4)
+        if count is None:
+            count = self._int64()
+        assert count.dtype == torch.int64 and count.numel() >= 1
+        words = run_encode_workspace_words(n)
+        if workspace is None:
+            workspace = self._running_workspace(words)
+        assert workspace.dtype == torch.int64 and workspace.numel() >= words
+        given = lambda t: t.data_ptr() if (t is not False and capacity) else None
+        check(lib().mi355_run_encode_dev(self._ctx, _col_ptr(col), n, col.c, ce, given(values), given(ends), capacity, count.data_ptr(),
+                                         workspace.data_ptr() if n else None))
+        return (None if values is False else values), (None if ends is False else ends), count
+
+    def count_runs(self, col: PackedColumn) -> torch.Tensor:
+        """int64[1] on the device: the number of runs of the column (rows that differ from the next row, and the last row).  Count
+        only: two launches, no output column.  No host read: the caller decides when to look"""
+        return self.run_encode(col, capacity=0, values=False, ends=False)[2]
+
+    def run_lengths(self, ends_col: PackedColumn, co: Optional[int] = None) -> PackedColumn:
+        """the run lengths of a column of run ends: delta(ends, first=0), at the ends' width unless `co` names one"""
+        return self.delta(ends_col, first=0, k=0, co=ends_col.c if co is None else co)
+
+    def run_decode(self, values_col: PackedColumn, ends_col: PackedColumn, n: int, runs=None, miss: int = 0, out: Optional[torch.Tensor] = None,
+                   uncovered: Optional[torch.Tensor] = None) -> PackedColumn:
+        """the column of n rows that the runs (values_col, ends_col) encode, packed at values_col.c bits: out[i] = values[j] for the
+        first run j whose end lies behind row i, `miss` for the rows behind the last run.  `runs`: how many of the tables' entries
+        count -- an int, or the int64[1] device tensor run_encode left (read on the device: nothing synchronises; at most
+        min(values_col.n, ends_col.n) either way); None: all of them.  Ends must be non-decreasing; equal neighbours are runs of
+        length zero (repeat).  `uncovered`: an int64[1] device tensor that gets the number of rows behind the last run (None:
+        not counted).  `out` as in arith.  With values_col.c == 1 the result is the bitmap over the rows of a bitmap over the
+        runs.  Capturable into a graph whatever its arguments; tables and `runs` are read at every replay."""
+        n = _unsigned(n, 1 << 64, "n {}")
+        table = min(values_col.n, ends_col.n)
+        runs_dev = None
+        if isinstance(runs, torch.Tensor):
+            assert runs.dtype == torch.int64 and runs.numel() >= 1
+            runs_dev, runs = runs, table
+        else:
+            runs = table if runs is None else _unsigned(runs, table + 1, f"runs {{}} beyond the tables' {table} entries")
+        runs = _unsigned(runs, 1 << 32, "runs {} beyond 2^32 - 1")
+        cv = values_col.c
+        miss = _unsigned(miss, 1 << cv, f"miss {{}} is no value of {cv} bits")
+        out = self._packed_out(out, cv, n, (n * cv + 7) // 8)
+        if uncovered is not None:
+            assert uncovered.dtype == torch.int64 and uncovered.numel() >= 1
+        check(lib().mi355_run_decode_dev(self._ctx, _col_ptr(values_col) if runs else None, cv, _col_ptr(ends_col) if runs else None, ends_col.c, runs,
+                                         _ptr(runs_dev), n, miss, out.data_ptr() if n else None, _ptr(uncovered)))
+        return PackedColumn(out, n, cv)
+
+    def repeat(self, values_col: PackedColumn, counts_col: PackedColumn, n: int, miss: int = 0, out: Optional[torch.Tensor] = None,
+               uncovered: Optional[torch.Tensor] = None) -> PackedColumn:
+        """repeat_interleave, packed: value j of values_col counts_col[j] times, on n rows -- running_sum(counts) at the width that
+        holds every partial sum (32 bits at the most), then run_decode.  Runs that end beyond n are cut at n; the rows behind the
+        sum of the counts get `miss`"""
+        fits = counts_col.n * ((1 << counts_col.c) - 1) < 1 << 32  # else: 32 bits, and a sum beyond them ends behind every row
+        ends, _ = self.running_sum(counts_col, co=None if fits else 32, miss=0 if fits else (1 << 32) - 1)
+        return self.run_decode(values_col, ends, n, miss=miss, out=out, uncovered=uncovered)
+
+    def runs_column(self, col: PackedColumn) -> Tuple[PackedColumn, PackedColumn]:
+        """`run_encode` as two columns (values, ends): reads the count back (the one host read the row count of a new column needs)"""
+        values, ends, count = self.run_encode(col)
+        r = int(count.item())
+        return PackedColumn(values, r, col.c), PackedColumn(ends, r, _ends_width(col.n, None))
 
     def compact(self, col: PackedColumn, bitmap: torch.Tensor, capacity: Optional[int] = None, out: Optional[torch.Tensor] = None):
         """the values of the rows of `col` whose bit is set in `bitmap` (a result bitmap of col.n rows), in row order, packed at

@@ -152,6 +152,13 @@ HEADERS["mi355_running.h"] = [
     ("mi355_delta_kernel", C.c_char_p, [C.c_uint, C.c_int64, C.c_uint]),
 ]
 
+# a packed column's positions in a sorted packed table.  (In front of mi355_runs.h: tests/test_runs.py wants that header and mi355_sort.h to stay the dict's last two keys.)
+HEADERS["mi355_search.h"] = [
+    ("mi355_search_sorted_dev", _int, [_vp, _vp, _u64, C.c_uint, _vp, C.c_uint, _u64, _vp, _int, _int, _u32, _vp, C.c_uint, _vp, _vp]),
+    ("mi355_search_sorted_kernel", C.c_char_p, [C.c_uint, C.c_uint, C.c_uint, _u64]),
+    ("mi355_search_sorted_stride", _u64, [_u64]),
+]
+
 # a packed column's runs as two packed columns, and their expansion.  (In front of mi355_sort.h too.)
 HEADERS["mi355_runs.h"] = [
     ("mi355_run_encode_dev", _int, [_vp, _vp, _u64, C.c_uint, C.c_uint, _vp, _vp, _u64, _vp, _vp]),

@@ -330,6 +330,23 @@ def run_decode_kernel(cv: int, ce: int) -> str:
     return s.decode()
 
 
+def search_sorted_kernel(c: int, ct: int, co: int, rows: int) -> str:
+    """kernel family ScanEngine.search_sorted launches for a column of width c, a table of `rows` entries of width ct and positions
+    of width co (mi355_search_sorted_kernel; arithmetic only, needs no device): 'search_lds_kernel' | 'search_global_kernel'.
+    A width outside 1..32 or rows outside 0..2^32 - 1 -> ValueError"""
+    ok = all(0 <= int(w) < 1 << 32 for w in (c, ct, co)) and 0 <= int(rows) < 1 << 64
+    s = lib().mi355_search_sorted_kernel(int(c), int(ct), int(co), int(rows)) if ok else None
+    if s is None:
+        raise ValueError((c, ct, co, rows))
+    return s.decode()
+
+
+def search_sorted_stride(rows: int) -> int:
+    """the distance S of the table samples a block of ScanEngine.search_sorted keeps in LDS (mi355_search_sorted_stride;
+    arithmetic only): 1 where the whole table fits"""
+    return int(lib().mi355_search_sorted_stride(_unsigned(rows, 1 << 32, "rows {} beyond 2^32 - 1")))
+
+
 def _ends_width(n: int, ends_width: Optional[int]) -> int:
     """the width of a column of run ends over n rows: the one that holds n itself (None), or the caller's when it does"""
     n = _unsigned(n, 1 << 32, "n {} beyond 2^32 - 1 rows: an end of at most 32 bits cannot hold it")
@@ -1028,6 +1045,89 @@ class ScanEngine:
         assert values.n == keys.n, "one value per key row"
         index, counts = self.key_index(keys, table_rows, mask=mask, keep=keep)
         return self.lookup(index, values, miss=miss), counts
+
+    _SIDE = {"left": 0, "right": 1}  # MI355_SEARCH_LEFT, MI355_SEARCH_RIGHT
+
+    def search_sorted(self, col: PackedColumn, table: PackedColumn, side: str = "left", rows=None, exact: bool = False, miss: int = 0,
+                      co: Optional[int] = None, out=None, found=None, hits=False):
+        """numpy.searchsorted, packed: for every row of `col` its position in the sorted packed column `table` -- the number of
+        entries < the value (side="left") or <= it (side="right") -> (positions PackedColumn of col.n values of co bits, found,
+        hits).  `rows`: how many of the table's entries count -- an int, or an int64[1] device tensor such as sort_rows,
+        run_encode or value_set leave (read on the device: nothing synchronises; at most table.n either way); None: all.
+        A row is FOUND when its value occurs in the table.  exact: a row that is not found gets `miss` for its position.
+        co: the positions' width (None: the smallest that holds the row bound, and `miss` when exact).  out: a uint8 device
+        tensor as in lookup (None: allocated; False: no positions, the first result is None).  found: a uint8 device tensor of
+        ceil(col.n / 8) bytes for the bitmap of found rows (True: allocated; None: no bitmap).  hits: an int64[1] device tensor
+        for the number of found rows (True: allocated; False: not counted).  Values compare as unsigned integers whatever the
+        two widths.  The table must be non-decreasing; on one that is not, positions stay inside 0..rows and nothing outside
+        the table is read.  Capturable into a graph whatever its arguments, with no warm-up; column, table and `rows` are read
+        at every replay."""
+        if side not in self._SIDE:
+            raise ValueError(f"side {side!r} is neither 'left' nor 'right'")
+        rows_dev = None
+        if isinstance(rows, torch.Tensor):
+            assert rows.dtype == torch.int64 and rows.numel() >= 1
+            rows_dev, rows = rows, table.n
+        else:
+            rows = table.n if rows is None else _unsigned(rows, table.n + 1, f"rows {{}} beyond the table's {table.n} entries")
+        rows = _unsigned(rows, 1 << 32, "rows {} beyond 2^32 - 1")
+        miss = _unsigned(miss, 1 << 32, "miss {} is no value of 32 bits")
+        if co is None:
+            co = max(1, rows.bit_length(), miss.bit_length() if exact else 0)
+        co = int(co)
+        if not 1 <= co <= 32:
+            raise ValueError(f"co {co} outside 1..32")
+        with_out = out is not False
+        if with_out:
+            if rows >= 1 << co:
+                raise ValueError(f"rows {rows} beyond 2^{co} - 1: a position is no value of {co} bits")
+            miss = _unsigned(miss, 1 << co, f"miss {{}} is no value of {co} bits")
+            out = self._packed_out(out, co, col.n, (col.n * co + 7) // 8)
+        if found is True:
+            found = self.alloc_bitmap(col.n)
+        if found is not None:
+            assert found.dtype == torch.uint8 and found.numel() >= (col.n + 7) // 8
+        if hits is True:
+            hits = self._int64()
+        elif hits is False:
+            hits = None
+        if hits is not None:
+            assert hits.dtype == torch.int64 and hits.numel() >= 1
+        assert with_out or found is not None or hits is not None, "neither positions, nor a bitmap, nor a count asked for"
+        check(lib().mi355_search_sorted_dev(self._ctx, _col_ptr(col), col.n, col.c, _col_ptr(table) if rows else None, table.c, rows, _ptr(rows_dev),
+                                            self._SIDE[side], 1 if exact else 0, miss, out.data_ptr() if with_out else None, co, _ptr(found), _ptr(hits)))
+        return (PackedColumn(out, col.n, co) if with_out else None), found, hits
+
+    def bucketize(self, col: PackedColumn, edges: PackedColumn, co: Optional[int] = None) -> PackedColumn:
+        """the bin of every row among sorted `edges`: the number of edges <= the value (0 below the first edge, edges.n from the last
+        on) -- width_bucket, a CASE WHEN ladder, an uneven histogram's keys (then `group_aggregate`)"""
+        return self.search_sorted(col, edges, side="right", co=co)[0]
+
+    def index_of(self, col: PackedColumn, table: PackedColumn, miss: int, rows=None, co: Optional[int] = None) -> PackedColumn:
+        """the first position of every row's value in the sorted `table`, `miss` where it does not occur: what `lookup` takes"""
+        return self.search_sorted(col, table, side="left", rows=rows, exact=True, miss=miss, co=co)[0]
+
+    def is_member(self, col: PackedColumn, table: PackedColumn, rows=None):
+        """`col IN (sorted table)` -> (bitmap of col.n rows, hits int64[1]); no positions are written"""
+        return self.search_sorted(col, table, rows=rows, out=False, found=True, hits=True)[1:]
+
+    def sorted_keys(self, keys: PackedColumn, mask: Optional[torch.Tensor] = None):
+        """the keys of the rows `mask` selects in ascending order, as the table `search_sorted` takes -> (PackedColumn of keys.n
+        entries at keys.c bits of which the first `count` are set, rowids int64[keys.n]: the row each came from, count int64[1]).
+        `sort_rows` with its values, packed; nothing synchronises.  Equal keys keep their row order."""
+        rowids, count, values = self.sort_rows(keys, mask=mask, with_values=True)
+        return self.compress(values, keys.c), rowids, count
+
+    def sparse_lookup(self, fk: PackedColumn, dim_keys: PackedColumn, dim_attr: PackedColumn, miss: int = 0,
+                      mask: Optional[torch.Tensor] = None) -> PackedColumn:
+        """`lookup` for keys without a dense domain: for every row of `fk` the value of `dim_attr` in the row of the dimension
+        whose key in `dim_keys` equals it (among the rows `mask` selects; the lowest such row where keys repeat), `miss` where
+        there is none, packed at dim_attr.c bits.  sorted_keys -> gather(dim_attr) in that order, packed -> index_of with the
+        dimension's row count for its miss -> lookup, which turns that into `miss`.  Nothing synchronises."""
+        assert dim_attr.n == dim_keys.n, "one attribute per dimension row"
+        table, rowids, count = self.sorted_keys(dim_keys, mask)
+        attr = self.compress(self.gather(dim_attr, rowids, count)[:dim_keys.n], dim_attr.c)
+        return self.lookup(self.index_of(fk, table, miss=dim_keys.n, rows=count), attr, miss=miss)
 
     def bitmap_combine(self, op: str, a: torch.Tensor, b: torch.Tensor, n: int, out: Optional[torch.Tensor] = None):
         if out is None:

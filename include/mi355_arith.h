@@ -48,7 +48,9 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: op outside the two; a width outside 1..32; b != 0 with
  *               MI355_ARITH_MUL; miss >= 2^co when co < 32; the range rule; out_of_range_dev misaligned; with n > 0 a null or
  *               misaligned packed1_dev, packed2_dev or out_dev, or out_dev overlapping an input.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the stores to out_dev: -1 (the default) write-through up to 768 MiB of
+ *               output, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernel the call launched.
  *   graph capture: capturable -- the call enqueues its one kernel on the context's stream and, when a counter is given, the
  *   8-byte zeroing of out_of_range_dev in front of it; it uploads nothing, takes no buffer of the context's pool and never

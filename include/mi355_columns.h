@@ -31,6 +31,8 @@ extern "C" {
  * nothing; both outputs NULL is MI355_E_INVALID.
  *   errors (MI355_E_INVALID, nothing launched, outputs untouched): op outside MI355_CMP_EQ .. MI355_CMP_NOT_BETWEEN,
  *   mask_op outside MI355_BITMAP_AND .. MI355_BITMAP_ANDNOT, a width outside 1..32, a misaligned or null column.
+ *   stores  option "scan_nt_stores" (mi355_scan.h) governs the bitmap stores: -1 (the default) write-through up to 768 MiB of
+ *   bitmap, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The bytes never depend on it.
  *   graph capture: capturable -- the call enqueues one kernel on the context's stream; it uploads nothing, takes no buffer
  *   of the context's pool and never synchronises, whatever its arguments. */
 MI355_API int mi355_scan_columns_dev(mi355_ctx *ctx, const void *packed1_dev, unsigned c1, const void *packed2_dev, unsigned c2,

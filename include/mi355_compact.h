@@ -38,7 +38,10 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: c outside 1..32; count_dev NULL; packed_dev or bitmap_dev
  *               NULL (n > 0); out_dev NULL (n > 0 and capacity > 0); a misaligned pointer; out_dev overlapping packed_dev or
  *               bitmap_dev.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs compact_kernel's stores of whole dwords: -1 (the default) write-through
+ *               up to 768 MiB of output, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The dwords that chunks
+ *               share leave by atomic OR whatever it says, and the bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernels the call launched; compact_kernel is among them when capacity > 0.
  *   graph capture: capturable after a warm-up call of at least this size -- the call takes the context's selection
  *   workspace, like mi355_bitmap_to_rowids_dev: (ceil(n / 16384) + 1 + ceil(n / 16777216)) words, grown outside capture only.

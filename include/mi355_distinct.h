@@ -75,7 +75,9 @@ MI355_API const char *mi355_value_set_kernel(unsigned c, uint64_t set_bits);
  *   errors      MI355_E_INVALID, nothing launched, nothing written: ct outside 1..32; miss >= 2^ct; set_bits > 2^32; set_dev or
  *               table_dev NULL with set_bits > 0; out_dev NULL; a misaligned pointer; the set's bytes overlapping the table's, or
  *               out_dev overlapping either.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs set_ranks_kernel's stores to table_dev: -1 (the default) write-through
+ *               up to 768 MiB of table, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the three kernels the call launched.
  *   graph capture: capturable after a warm-up call of at least the same set_bits -- the call takes the context's selection
  *   workspace, like mi355_compact_dev: (ceil(set_bits / 16384) + 1 + ceil(set_bits / 16777216)) words, grown outside capture

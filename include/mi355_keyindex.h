@@ -57,7 +57,10 @@ extern "C" {
  *               first_row >= 2^32; miss >= 2^ct; a keep that is neither constant; keys_dev NULL (n > 0); table_dev NULL
  *               (table_rows > 0); out_dev NULL; a misaligned pointer; the table's bytes [table_dev, table_dev +
  *               ceil(table_rows * ct / 8)) overlapping the keys, the mask or out_dev.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs key_index_pack_kernel's stores to table_dev: -1 (the default)
+ *               write-through up to 768 MiB of table, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The bytes
+ *               never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the tier's kernel, then key_index_pack_kernel; with n == 0 only the latter (the table
  *               is all `miss`, no workspace is used), with table_rows == 0 only the former.
  *   graph capture: capturable after a warm-up call of at least the same table_rows -- the call takes the context's selection

@@ -45,7 +45,9 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: c or ct outside 1..32; table_rows > 2^32; miss >= 2^ct;
  *               packed_dev or out_dev NULL (n > 0); table_dev NULL with table_rows > 0; a misaligned pointer; out_dev
  *               overlapping packed_dev or table_dev.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the stores to out_dev: -1 (the default) write-through up to 768 MiB of
+ *               output, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernel the call launched.
  *   graph capture: capturable -- the call enqueues its one kernel on the context's stream; it uploads nothing, takes no
  *   buffer of the context's pool and never synchronises, whatever its arguments.  The table is read at every replay: a graph of

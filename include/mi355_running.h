@@ -56,7 +56,9 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, every output and the workspace untouched: a width outside 1..32; flags outside
  *               the two; miss >= 2^co when co < 32; the range rule; result_dev or mask_dev misaligned; with n > 0 a null or
  *               misaligned packed_dev, out_dev or ws_dev, or out_dev overlapping the column, the mask or the workspace.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the stores to out_dev: -1 (the default) and 0 plain.  1 non-temporal,
+ *               2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the three kernels in launch order.
  *   graph capture: capturable -- the call enqueues its three kernels and, when result_dev is given, the 16-byte zeroing of it on
  *   the context's stream; the chunk prefix lives in the caller's workspace, so it uploads nothing, takes no buffer of the context's
@@ -93,7 +95,9 @@ MI355_API uint64_t mi355_running_sum_workspace_words(uint64_t n);
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: a width outside 1..32; first >= 2^c when c < 32;
  *               miss >= 2^co when co < 32; out_of_range_dev misaligned; with n > 0 a null or misaligned packed_dev or out_dev, or
  *               out_dev overlapping the column.
- *   record      mi355_ctx_last_launch names the kernel the call launched.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the stores to out_dev: -1 (the default) and 0 plain.  1 non-temporal,
+ *               2 write-through.  The bytes never depend on it.
+ *   record     mi355_ctx_last_launch names the kernel the call launched.
  *   graph capture: capturable -- the call enqueues its one kernel on the context's stream and, when a counter is given, the
  *   8-byte zeroing of out_of_range_dev in front of it; it uploads nothing, takes no buffer of the context's pool and never
  *   synchronises, whatever its arguments.  The column is read at every replay. */

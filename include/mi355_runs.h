@@ -44,7 +44,10 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, every output and the workspace untouched: a width outside 1..32;
  *               n > 2^ce - 1; count_dev NULL or misaligned; with n > 0 a null or misaligned packed_dev or ws_dev; with
  *               capacity > 0 both outputs NULL; an output not 16 bytes aligned; any overlap named above.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs run_emit_kernel's stores of whole dwords to both outputs: -1 (the
+ *               default) and 0 plain.  1 non-temporal, 2 write-through.  The dwords that chunks share leave by atomic OR whatever
+ *               it says, and the bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernels in launch order.
  *   graph capture: capturable -- the call enqueues its kernels and the 8-byte zeroing of count_dev on the context's stream; the
  *   chunk prefix lives in the caller's workspace, so it uploads nothing, takes no buffer of the context's pool, never synchronises
@@ -84,7 +87,9 @@ MI355_API uint64_t mi355_run_encode_workspace_words(uint64_t n);
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: a width outside 1..32; miss >= 2^cv when cv < 32;
  *               runs > 2^32 - 1; runs_dev or uncovered_dev misaligned; with n > 0 a null or misaligned out_dev; with n > 0 and
  *               runs > 0 a null or misaligned values_dev or ends_dev, or out_dev overlapping a table.
- *   record      mi355_ctx_last_launch names the kernel.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the stores to out_dev: -1 (the default) and 0 plain.  1 non-temporal,
+ *               2 write-through.  The bytes never depend on it.
+ *   record     mi355_ctx_last_launch names the kernel.
  *   graph capture: capturable -- the call enqueues its one kernel on the context's stream and, when a counter is given, the
  *   8-byte zeroing of uncovered_dev in front of it; it uploads nothing, takes no buffer of the context's pool and never
  *   synchronises, whatever its arguments.  Both tables and *runs_dev are read at every replay. */

@@ -65,7 +65,10 @@ extern "C" {
  *               MI355_SEARCH_LEFT nor MI355_SEARCH_RIGHT; rows > 2^32 - 1; with out_dev rows > 2^co - 1, or miss >= 2^co when
  *               co < 32; with n > 0 out_dev, found_dev and hits_dev all NULL; a misaligned pointer; with n > 0 packed_dev NULL; with
  *               rows > 0 table_dev NULL; any overlap named above.
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the stores to out_dev and found_dev alike: -1 (the default)
+ *               write-through up to 768 MiB of positions and bitmap together, non-temporal beyond; 0 plain.  1 non-temporal,
+ *               2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernel the call launched.
  *   graph capture: capturable -- the call enqueues its one kernel on the context's stream and, when a counter is given, the
  *   8-byte zeroing of hits_dev in front of it; it uploads nothing, takes no buffer of the context's pool, no scratch of the

@@ -41,7 +41,10 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: c outside 1..32; set_bits > 2^32; packed_dev NULL (n > 0);
  *               set_dev NULL with set_bits > 0; bitmap_dev and hits_dev both NULL; a misaligned pointer; set_dev overlapping
  *               bitmap_dev (the byte ranges [set_dev, set_dev + ceil(set_bits/8)) and [bitmap_dev, bitmap_dev + ceil(n/8))).
- *   stream      asynchronous on the context's stream; the call holds the context's lock like every other.
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs the bitmap stores of both kernels: -1 (the default) write-through up
+ *               to 768 MiB of bitmap, non-temporal beyond; 0 write-through too (the kernels have no plain form, like
+ *               mi355_scan2_dev's).  1 non-temporal, 2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream; the call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernel the call launched.
  *   graph capture: capturable -- the call enqueues its one kernel on the context's stream; it uploads nothing, takes no
  *   buffer of the context's pool and never synchronises, whatever its arguments.  The set is read at every replay: a graph of

@@ -46,7 +46,9 @@ extern "C" {
  *   errors      MI355_E_INVALID, nothing launched, outputs untouched: c outside 1..32; bitmap_dev (n > 0) or result_dev NULL;
  *               packed_dev NULL (n > 0); a misaligned pointer; an output overlapping the column, or the mask other than
  *               bitmap_dev == mask_dev.
- *   stream      asynchronous on the context's stream, without a host round trip: threshold, remaining k and every decision stay
+ *   stores      option "scan_nt_stores" (mi355_scan.h) governs topk_emit_kernel's bitmap stores: -1 (the default) write-through up to
+ *               768 MiB of bitmap, non-temporal beyond; 0 plain.  1 non-temporal, 2 write-through.  The bytes never depend on it.
+ *   stream     asynchronous on the context's stream, without a host round trip: threshold, remaining k and every decision stay
  *               on the device.  The call holds the context's lock like every other.
  *   record      mi355_ctx_last_launch names the kernels the call launched.
  *   graph capture: capturable after a warm-up call of at least this size -- the call takes the context's selection

@@ -1,7 +1,8 @@
 """What the test files share: where things are, the library and engine fixtures, what a public header declares, a recording
 stand-in for the library, launch records, guarded buffers and the exact image of one, packed and hostile uploads, the runtime of
-the alignment tables, the rank-process helpers, the checks every feature header and feature source directory gets, and which entry
-points' launchers reach a piece of the context's state.  capture.py (graph capture) and
+the alignment tables, what the unit tables compute their inputs and expectations with (numpy and the CPU oracle), the rank-process
+helpers, the checks every feature header and feature source directory gets, which entry points' launchers reach a piece of the
+context's state, and which kernels of a feature directory take a store policy.  capture.py (graph capture) and
 kernel_cases.py (the kernel-path case table) stand beside it; no test file imports from another test file.
 
 A plain module, not a conftest: a test file imports what it uses by name, fixtures included (pytest takes an imported fixture as
@@ -16,6 +17,7 @@ import socket
 import subprocess
 import time
 import types
+import zlib
 
 import numpy as np
 import pytest
@@ -292,6 +294,87 @@ def hostile_bitmap(bits, offset=0, front=None):
     return view, buf
 
 
+# ---- what the unit tables (test_shared_state, test_store_policies) compute their inputs and expectations with: numpy and the CPU
+# oracle only ----
+
+CMP = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "between": 6, "not_between": 7}  # MI355_CMP_*
+BOP = {"and": 0, "or": 1, "xor": 2, "andnot": 3}                                             # MI355_BITMAP_*
+
+
+def oracle():
+    from oracle import oracle as get
+
+    return get()
+
+
+def rng_of(*key):
+    return np.random.default_rng(zlib.crc32(repr(key).encode()))
+
+
+def u64s(*xs):
+    return np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in xs], dtype=np.uint64).view(np.uint8)
+
+
+def packed(vals, c):
+    """the column as the calls read it: the oracle's image, pad included"""
+    return oracle().pack(np.ascontiguousarray(vals, dtype=np.uint32), c)
+
+
+def payload(vals, c):
+    """the bytes a call that writes len(vals) values of c bits leaves: trailing bits of the last byte zero"""
+    return packed(vals, c)[: (len(vals) * c + 7) // 8].copy()
+
+
+def prefix_body(nbytes, written):
+    """a buffer of nbytes whose first len(written) bytes a call writes; the rest stays as it was"""
+    body = np.full(nbytes, SENTINEL, dtype=np.uint8)
+    body[: len(written)] = written
+    return body
+
+
+def random_values(rng, n, c):
+    return rng.integers(0, 1 << c, n, dtype=np.uint64).astype(np.uint32)
+
+
+def pred(v, op, a, b=0):
+    v = v.astype(np.int64)
+    between = (v >= a) & (v <= b)
+    return {"==": v == a, "!=": v != a, "<": v < a, "<=": v <= a, ">": v > a, ">=": v >= a, "between": between, "not_between": ~between}[op]
+
+
+def combine(p, m, op):
+    return {"and": p & m, "or": p | m, "xor": p ^ m, "andnot": m & ~p}[op]
+
+
+def top_k_expect(vals, qual, k, largest):
+    """-> (the bitmap's rows, [m, threshold, selected rows beyond it, qualifying rows equal to it]): by value, then by row id"""
+    idx = np.nonzero(qual)[0]
+    v = vals[idx].astype(np.int64)
+    m = min(k, len(idx))
+    bits = np.zeros(len(vals), dtype=bool)
+    if m == 0:
+        return bits, [0, 0, 0, 0]
+    order = np.lexsort((idx, -v if largest else v))
+    bits[idx[order[:m]]] = True
+    T = int(v[order[m - 1]])
+    return bits, [m, T, int((v > T).sum() if largest else (v < T).sum()), int((v == T).sum())]
+
+
+def key_index_expect(keys, qual, table_rows, keep, first_row, ct, miss):
+    """-> (table, [members, selected rows outside the table, selected rows inside it, members whose row id did not fit])"""
+    rows = np.nonzero(qual & (keys < table_rows))[0]
+    winner = np.full(table_rows, -1, dtype=np.int64)
+    if keep == "first":
+        winner[keys[rows[::-1]]] = rows[::-1]
+    else:
+        winner[keys[rows]] = rows
+    member = winner >= 0
+    ids = winner + first_row
+    fits = member & (ids < (1 << ct))
+    table = np.where(fits, ids, miss).astype(np.uint32)
+    return table, [int(member.sum()), int((qual & (keys >= table_rows)).sum()), len(rows), int((member & ~fits).sum())]
+
+
 def corner_rows(n, R=2048):
     """rows that carry the corner values (tiles of R rows: 64 lanes x 32 rows): the first four of the first tile, the last four of
     the last full tile, the last four of the ragged tail (as far as they exist)"""
@@ -488,6 +571,27 @@ def entry_points_reaching(*needles):
     reach = {name for name, _ in reach}
     exported = {s for header in sorted(os.listdir(INCLUDE)) if header.endswith(".h") for s in declared(header)}
     return sorted(s for s in reach & exported if s.endswith("_dev"))
+
+
+def feature_directories():
+    """the directories under csrc/ that hold a feature's own kernels and launcher (kernels/ and extras/ are the shared ones)"""
+    return sorted(d for d in os.listdir(CSRC) if os.path.isdir(os.path.join(CSRC, d)) and d not in ("kernels", "extras"))
+
+
+def store_policy_kernels(feature):
+    """the name of every __global__ under csrc/<feature>/ that takes a struct with an `nts` field, or an AUX template argument"""
+    text = "\n".join(re.sub(r"//[^\n]*|/\*.*?\*/", "", open(path).read(), flags=re.S) for path in feature_sources(feature))
+    with_field = {m.group(1) for m in re.finditer(r"^struct (\w+) \{\n(.*?)\n\};", text, flags=re.M | re.S) if re.search(r"\bnts;", m.group(2))}
+    found = set()
+    for m in re.finditer(r"(?:template <([^>]*)>\s*)?(?:static )?__global__[^;{]*?\bvoid\s+(\w+)\s*\(\s*(\w+)\s+\w+\s*\)", text):
+        if m.group(3) in with_field or re.search(r"\bint AUX", m.group(1) or ""):
+            found.add(m.group(2))
+    return found
+
+
+def assignments_to(field):
+    """[(function, file, right-hand side)] of every `.<field> = ...;` in a function that a .hip file under csrc/ defines"""
+    return [(name, path, rhs.strip()) for name, path, body in hip_functions() for rhs in re.findall(rf"\.{field}\s*=\s*([^;]+);", body)]
 
 
 def gpu_part_of(test_file):

@@ -17,15 +17,15 @@ queued workspace work; graph replays between eager calls of other features.
 """
 import ctypes as C
 import dataclasses
-import zlib
 
 import numpy as np
 import pytest
 
 import capture
 from kernel_cases import CASES, WHERE_CHAIN, WHERE_COUNT_CASES, WHERE_LUT, WHERE_LUT_MULTI, column
-from support import (E_INVALID, SENTINEL, Expected, Guarded, L, base_name, eng, entry_points_reaching, header_macro, header_text,  # noqa: F401
-                     packbits, parse_record)
+from support import (BOP, CMP, E_INVALID, SENTINEL, Expected, Guarded, L, base_name, combine, eng, entry_points_reaching, header_macro,  # noqa: F401
+                     header_text, key_index_expect, packbits, packed, parse_record, payload, pred, prefix_body, random_values, rng_of, top_k_expect,
+                     u64s)
 
 gpu = pytest.mark.gpu
 
@@ -37,9 +37,6 @@ N_SCRATCH_TWIN = 57 * 8192 + 99
 CHUNK = 16384
 SCAN_GROUP = 1024
 
-CMP = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "between": 6, "not_between": 7}  # MI355_CMP_*
-BOP = {"and": 0, "or": 1, "xor": 2, "andnot": 3}                                             # MI355_BITMAP_*
-
 # entry points whose launcher reaches the state without being a unit, each with the reason
 EXEMPT = {
     "mi355_decompress_dev": "goes through the width groups' launch(), which fills the scratch pointer of every request; decompress_kernel takes DecompArgs, "
@@ -49,51 +46,6 @@ EXEMPT = {
     "mi355_sharded_scan_eq_dev": "needs a communicator; its scan is mi355_scan_eq_dev (test_exchange_loopback runs it)",
     "mi355_sharded_scan_range_dev": "needs a communicator; its scan is mi355_scan_range_dev (test_exchange_loopback runs it)",
 }
-
-
-def oracle():
-    from oracle import oracle as get
-
-    return get()
-
-
-def rng_of(*key):
-    return np.random.default_rng(zlib.crc32(repr(key).encode()))
-
-
-def u64s(*xs):
-    return np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in xs], dtype=np.uint64).view(np.uint8)
-
-
-def packed(vals, c):
-    """the column as the calls read it: the oracle's image, pad included"""
-    return oracle().pack(np.ascontiguousarray(vals, dtype=np.uint32), c)
-
-
-def payload(vals, c):
-    """the bytes a call that writes len(vals) values of c bits leaves: trailing bits of the last byte zero"""
-    return packed(vals, c)[: (len(vals) * c + 7) // 8].copy()
-
-
-def prefix_body(nbytes, written):
-    """a buffer of nbytes whose first len(written) bytes a call writes; the rest stays as it was"""
-    body = np.full(nbytes, SENTINEL, dtype=np.uint8)
-    body[: len(written)] = written
-    return body
-
-
-def random_values(rng, n, c):
-    return rng.integers(0, 1 << c, n, dtype=np.uint64).astype(np.uint32)
-
-
-def pred(v, op, a, b=0):
-    v = v.astype(np.int64)
-    between = (v >= a) & (v <= b)
-    return {"==": v == a, "!=": v != a, "<": v < a, "<=": v <= a, ">": v > a, ">=": v >= a, "between": between, "not_between": ~between}[op]
-
-
-def combine(p, m, op):
-    return {"and": p & m, "or": p | m, "xor": p ^ m, "andnot": m & ~p}[op]
 
 
 # ---- the workspace's footprint per call, in 64-bit words, as the headers document it ----------------------------------------
@@ -280,20 +232,6 @@ def make_compact(c, above, density=0.4):
     return make
 
 
-def top_k_expect(vals, qual, k, largest):
-    """-> (the bitmap's rows, [m, threshold, selected rows beyond it, qualifying rows equal to it]): by value, then by row id"""
-    idx = np.nonzero(qual)[0]
-    v = vals[idx].astype(np.int64)
-    m = min(k, len(idx))
-    bits = np.zeros(len(vals), dtype=bool)
-    if m == 0:
-        return bits, [0, 0, 0, 0]
-    order = np.lexsort((idx, -v if largest else v))
-    bits[idx[order[:m]]] = True
-    T = int(v[order[m - 1]])
-    return bits, [m, T, int((v > T).sum() if largest else (v < T).sum()), int((v == T).sum())]
-
-
 def make_top_k(c, largest):
     def make(n, key):
         rng = rng_of(key)
@@ -341,21 +279,6 @@ def make_set_ranks(ct, miss):
                     outs={"table": payload(table, ct), "counts": u64s(members, unfit)},
                     call=lambda L, ctx, i, o: L.mi355_set_ranks_dev(ctx, i["set"], n, ct, miss, o["table"], o["counts"]))
     return make
-
-
-def key_index_expect(keys, qual, table_rows, keep, first_row, ct, miss):
-    """-> (table, [members, selected rows outside the table, selected rows inside it, members whose row id did not fit])"""
-    rows = np.nonzero(qual & (keys < table_rows))[0]
-    winner = np.full(table_rows, -1, dtype=np.int64)
-    if keep == "first":
-        winner[keys[rows[::-1]]] = rows[::-1]
-    else:
-        winner[keys[rows]] = rows
-    member = winner >= 0
-    ids = winner + first_row
-    fits = member & (ids < (1 << ct))
-    table = np.where(fits, ids, miss).astype(np.uint32)
-    return table, [int(member.sum()), int((qual & (keys >= table_rows)).sum()), len(rows), int((member & ~fits).sum())]
 
 
 def make_key_index(ck, table_rows, keep, masked, kernel, ct=None, permutation=False):

@@ -159,6 +159,13 @@ HEADERS["mi355_search.h"] = [
     ("mi355_search_sorted_stride", _u64, [_u64]),
 ]
 
+# sum, count, min, max of a packed column per run of a table of run ends.  (In front of mi355_runs.h too.)
+HEADERS["mi355_run_aggregate.h"] = [
+    ("mi355_run_aggregate_dev", _int, [_vp, _vp, C.c_uint, _u64, _vp, _vp, C.c_uint, _u64, _vp, _vp, _vp]),
+    ("mi355_run_aggregate_kernel", C.c_char_p, [C.c_uint, C.c_uint]),
+    ("mi355_run_aggregate_span_slots", _u32, [C.c_uint]),
+]
+
 # a packed column's runs as two packed columns, and their expansion.  (In front of mi355_sort.h too.)
 HEADERS["mi355_runs.h"] = [
     ("mi355_run_encode_dev", _int, [_vp, _vp, _u64, C.c_uint, C.c_uint, _vp, _vp, _u64, _vp, _vp]),

@@ -2,8 +2,9 @@
 stand-in for the library, launch records, guarded buffers and the exact image of one, packed and hostile uploads, the runtime of
 the alignment tables, what the unit tables compute their inputs and expectations with (numpy and the CPU oracle), the rank-process
 helpers, the checks every feature header and feature source directory gets, which entry points' launchers reach a piece of the
-context's state, and which kernels of a feature directory take a store policy.  capture.py (graph capture) and
-kernel_cases.py (the kernel-path case table) stand beside it; no test file imports from another test file.
+context's state, and which kernels of a feature directory take a store policy.  capture.py (graph capture),
+kernel_cases.py (the kernel-path case table) and large_routes.py (the torch routes of test_large_columns.py) stand beside it; no
+test file imports from another test file.
 
 A plain module, not a conftest: a test file imports what it uses by name, fixtures included (pytest takes an imported fixture as
 the importing module's own, so the module-scoped ones still live once per test file).  A copy that differs from what is here
@@ -194,6 +195,15 @@ class Guarded:
     @property
     def ptr(self):
         return C.c_void_p(self.t.data_ptr() + self.front)
+
+    @property
+    def body(self):
+        """the buffer between the guards, as a view"""
+        return self.t[self.front: self.front + self.nbytes]
+
+    def guards_intact(self):
+        """both guard regions still hold 0xEE, compared on the device: for a buffer too large for fetch()"""
+        return bool((self.t[: self.front] == SENTINEL).all().item()) and bool((self.t[self.front + self.nbytes:] == SENTINEL).all().item())
 
     def fetch(self):
         h = self.t.cpu().numpy()
